@@ -11,7 +11,10 @@ Prefill, fast-forward and warmup steps are outside the timed region; inputs (wei
 The K timed steps are CENTRED on the middle of the utterances' lives (decode step (max_model_len - longest prompt) / 2, where the
 context equals the whole-run mean, ~560 tokens for C3) whatever K is: the engine is fast-forwarded with untimed decode steps
 first, so `--steps 20` and `--steps 800` measure the same operating point (config.ctx_first / ctx_last say which).
-`e2e` (same JSON line) is the figure SURVEY.md 8(d) asks for beside it: the 32 utterances from `add_request` to their last token
+K larger than one life of the utterances holds (856 - W decode steps for C3) is honoured too: the batch is run again from its
+prompts as often as needed, the K steps shared evenly among these lives and each life's window centred the same way
+(config.lives / config.windows); `value` and `ms_per_step` are over all K steps, prefill and fast-forward of every life untimed.
+`e2e` (same JSON line, with `--full`) is the figure SURVEY.md 8(d) asks for beside it: the 32 utterances from `add_request` to their last token
 (prefill + all 884 / 859 decode steps), tokens / wall, with the per-request RTF distribution (the reference's own clock is the wall
 time of its generate call, tts.py:444,466-467; RTF_i = (finished - admitted) / (n_tokens_i / 25)).
 
@@ -28,7 +31,15 @@ utterance (2 CFG rows); default 200 timed steps centred on decode step 146.
 Every line carries step_ms_p50 / p90 / p99: the distribution of the timed steps' own durations (t3_step_times: from the completion of
 the step before to the step's completion, on the host clock that waits on the step's event).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+A plain run does what `value` needs and no more: set up, prefill, fast-forward, W warmup steps, the K timed steps, the result line.
+`--full` adds the legs that take runs of their own -- the two HIP-event passes behind `roofline`, the whole-utterance `e2e` leg and the
+oracle's `cpu_baseline` (each of which `--no-profile-pass` / `--no-e2e` / `--no-cpu-baseline` still drops).  The C4 line needs its
+stream run to the end for `rtf_p50`, so `--workload c4` does the same work with and without `--full`.
+`--dump-outputs DIR` writes what the caller of the timed path holds after the last timed step as DIR/<name>.npy (float32): `tokens`
+[utterances, n] = every utterance's speech-token ids from its first token to the one the last timed step sampled, and
+`last_step_tokens` [utterances] = that step's ids alone.  (c4: every request's ids to its end, rows padded with -1, and `lengths`.)
+The inputs are seeded, so two builds given the same arguments can be compared file for file.
 N > 1: one rank per GPU over RCCL.  Launched without WORLD_SIZE in the environment, this process starts the N ranks itself
 (`python -m torch.distributed.run ... bench.py`, before it touches the GPU) and relays rank 0's JSON line.
 """
@@ -60,6 +71,8 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile-pass", action="store_true")
     ap.add_argument("--no-e2e", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run the roofline passes, the whole-utterance e2e leg and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the timed path's outputs after its last step as DIR/<name>.npy")
     a = ap.parse_args()
     if a.workload == "c2":
         a.batch = 1
@@ -81,29 +94,50 @@ def longest_prompt(args):
     return T_C2 if getattr(args, "workload", "c3") == "c2" else T_ES
 
 
-def plan_window(args):
+def decode_steps_available(args):
+    return args.max_model_len - longest_prompt(args) - 3  # decode steps every utterance of the batch can take
+
+
+def plan_window(args, steps=None):
     """(fast-forward steps, first timed decode step, last timed decode step + 1): the timed window is centred on the run midpoint."""
-    g_min = args.max_model_len - longest_prompt(args) - 3  # decode steps every utterance of the batch can take
-    if args.steps + args.warmup > g_min:
-        sys.exit(f"steps + warmup must be <= {g_min} for this workload")
+    steps = args.steps if steps is None else steps
+    g_min = decode_steps_available(args)
+    if steps + args.warmup > g_min:
+        sys.exit(f"steps + warmup must be <= {g_min} for one life of this workload's utterances")
     centre = (args.max_model_len - longest_prompt(args)) // 2
-    ff = max(0, min(centre - args.steps // 2 - args.warmup, g_min - args.steps - args.warmup))
+    ff = max(0, min(centre - steps // 2 - args.warmup, g_min - steps - args.warmup))
     first = 1 + ff + args.warmup                         # the prefill step samples token 0
-    return ff, first, first + args.steps
+    return ff, first, first + steps
 
 
-def workload_string(args, first, last):
+def plan_lives(args):
+    """--steps K beyond what one life of the utterances holds: the batch is run again from its prompts as often as needed (same
+    seeds, so the same ids), the K timed steps shared evenly among the lives and each life's window centred like a single one.
+    Returns one (fast-forward steps, first, last) per life; the spans last - first add up to K exactly."""
+    cap = decode_steps_available(args) - args.warmup
+    if cap < 1:
+        sys.exit(f"warmup must be < {decode_steps_available(args)} for this workload")
+    n = -(-args.steps // cap)
+    spans = [args.steps // n + (1 if i < args.steps % n else 0) for i in range(n)]
+    return [plan_window(args, s) for s in spans]
+
+
+def lives_note(lives):
+    return f" in the first of {lives} lives of the batch (the windows of all lives are timed; config.windows)" if lives > 1 else ""
+
+
+def workload_string(args, first, last, lives=1):
     if getattr(args, "workload", "c3") == "c2":
         tag = "C2" if (args.max_model_len, args.layers) == (400, 30) else "custom (NOT a BASELINE.json config)"
         return (f"{tag}: t3-model (English, {args.layers}-layer Llama_520M, vocab 704), batch 1 (the 20-word sentence of C1, T={T_C2}), "
                 f"max_model_len={args.max_model_len} -> G={args.max_model_len - T_C2} tokens, CFG dual stream (2 rows/step), temperature 0.8 / top-p 0.8 / "
-                f"repetition penalty 2.0, stop id masked; timed window = decode steps [{first}, {last}) of the utterance")
+                f"repetition penalty 2.0, stop id masked; timed window = decode steps [{first}, {last}) of the utterance") + lives_note(lives)
     b_en = args.batch // 2
     is_c3 = (args.batch, args.max_model_len, args.layers) == (32, 1000, 30)
     tag = "C3" if is_c3 else "custom (NOT a BASELINE.json config)"
     return (f"{tag}: t3-model-multilingual ({args.layers}-layer Llama_520M, vocab 2454), {b_en} en (T={T_EN}) + {args.batch - b_en} es (T={T_ES}) "
             f"utterances per GPU, max_model_len={args.max_model_len}, CFG dual stream ({2 * args.batch} rows/step), temperature 0.8 / top-p 0.8 / "
-            f"repetition penalty 2.0, stop id masked; timed window = decode steps [{first}, {last}) of every utterance")
+            f"repetition penalty 2.0, stop id masked; timed window = decode steps [{first}, {last}) of every utterance") + lives_note(lives)
 
 
 def check_gpu_count(world):
@@ -200,7 +234,22 @@ def rtf_stats(eng, reqs, n_tokens):
             "rtf_definition": "T3 wall time of request i from admission to its last token / (n_tokens_i / 25 tokens per second of audio); incl_queue: from add_request"}
 
 
-def run_pass(eng, reqs, cond, ff, warmup, steps, sync, profile=False, only=None):
+def dump_outputs(path, rows, n_cols=None):
+    """rows = one list of token ids per utterance -> path/tokens.npy [len(rows), n] float32 (ids < 2^24 are exact), padded with -1."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    n = max(len(r) for r in rows) if n_cols is None else n_cols
+    tok = np.full((len(rows), n), -1.0, dtype=np.float32)
+    for i, r in enumerate(rows):
+        tok[i, :len(r)] = r[:n]
+    np.save(os.path.join(path, "tokens.npy"), tok)
+    if n_cols is None:
+        np.save(os.path.join(path, "lengths.npy"), np.asarray([len(r) for r in rows], dtype=np.float32))
+    else:
+        np.save(os.path.join(path, "last_step_tokens.npy"), np.ascontiguousarray(tok[:, n - 1]))
+
+
+def run_pass(eng, reqs, cond, ff, warmup, steps, sync, profile=False, only=None, keep_tokens=False):
     """prefill (untimed) -> fast-forward + warmup decode steps -> barrier -> K timed decode steps -> barrier.  Returns dict."""
     import torch
     for rid, prompt, sp in reqs:
@@ -230,9 +279,11 @@ def run_pass(eng, reqs, cond, ff, warmup, steps, sync, profile=False, only=None)
     kern = {k: eng.kernel_ms(k) for k in __import__("chatterbox_vllm2_amd.engine", fromlist=["x"]).KERNEL_CLASSES} if profile else {}
     # drain: finish the utterances quickly (not timed) so the engine is reusable
     eng.run_until_done()
+    # the ids every utterance had when the last timed step completed: token 0 from the prefill step, one per decode step after it
+    tokens = [eng.get_output(rid)[0][:1 + ff + warmup + steps] for rid, _, _ in reqs] if keep_tokens else None
     for rid, _, _ in reqs:
         eng.release(rid)
-    return dict(dt=dt, prefill_s=prefill_s, prefill_steps=n_pref, stats=st, kern=kern, step_ms=step_ms)
+    return dict(dt=dt, prefill_s=prefill_s, prefill_steps=n_pref, stats=st, kern=kern, step_ms=step_ms, tokens=tokens)
 
 
 def run_e2e(eng, reqs, cond):
@@ -257,7 +308,7 @@ def run_e2e(eng, reqs, cond):
     return out
 
 
-def run_c4(eng, reqs, cond, warmup, steps, sync):
+def run_c4(eng, reqs, cond, warmup, steps, sync, dump=None):
     """Continuous batching: all requests queued, W untimed steps, barrier, EXACTLY K timed engine steps, barrier, then the rest of the
     stream (untimed for `value`, but inside the e2e wall clock)."""
     import torch
@@ -286,6 +337,8 @@ def run_c4(eng, reqs, cond, warmup, steps, sync):
     dt_all = time.perf_counter() - t_all
     n_tokens = {rid: len(eng.get_output(rid)[0]) for rid, _, _ in reqs}
     total = sum(n_tokens.values())
+    if dump:
+        dump_outputs(dump, [eng.get_output(rid)[0] for rid, _, _ in reqs])
     e2e = {"value": round(total / dt_all, 2), "unit": "speech-tokens/s (this rank)", "tokens": total, "wall_s": round(dt_all, 4), "requests": len(reqs),
            "audio_seconds_per_second": round(total / S3_TOKEN_RATE / dt_all, 1),
            "includes": "admission, chunked prefill interleaved with decode, every decode step, retirement"}
@@ -355,7 +408,8 @@ def dominant_kernel_roofline(prof, dom_only, args):
 
 def main():
     args = parse()
-    ff, first, last = plan_window(args) if args.workload != "c4" else (0, 0, 0)
+    lives = plan_lives(args) if args.workload != "c4" else [(0, 0, 0)]
+    ff, first, last = lives[0]
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args)
     import torch
@@ -415,7 +469,7 @@ def main():
 
     if args.workload == "c4":
         reqs, n_global, c4 = build_c4_requests(E, args, rank, world)
-        window, e2e = run_c4(eng, reqs, cond, args.warmup, args.steps, sync)
+        window, e2e = run_c4(eng, reqs, cond, args.warmup, args.steps, sync, dump=args.dump_outputs if rank == 0 else None)
         dt = max_over_ranks(window["dt"])
         tokens = sum_over_ranks(window["tokens"])
         e2e_tokens = sum_over_ranks(e2e["tokens"]); e2e_wall = max_over_ranks(e2e["wall_s"])
@@ -449,19 +503,31 @@ def main():
         return
 
     reqs = build_requests(E, args, rank)
-    res = run_pass(eng, reqs, cond, ff, args.warmup, args.steps, sync, profile=False)
-    dt = max_over_ranks(res["dt"])
-    st = res["stats"]
+    import numpy as np
+    dt, step_ms, acc = 0.0, [], dict(algo_bytes_decode=0.0, decode_steps=0, sum_ctx_decode=0.0, decode_rows=0)
+    for i, (ff_i, first_i, last_i) in enumerate(lives):          # one life of the batch per entry; only the last one's ids are dumped
+        res = run_pass(eng, reqs, cond, ff_i, args.warmup, last_i - first_i, sync, profile=False,
+                       keep_tokens=bool(args.dump_outputs) and rank == 0 and i == len(lives) - 1)
+        dt += max_over_ranks(res["dt"])
+        step_ms.append(res["step_ms"])
+        for k in acc:
+            acc[k] += getattr(res["stats"], k)
+    st = argparse.Namespace(**acc)
+    step_ms = np.concatenate(step_ms)
+    assert len(step_ms) == args.steps == st.decode_steps
+    if res["tokens"] is not None:
+        assert all(len(t) == lives[-1][2] for t in res["tokens"])
+        dump_outputs(args.dump_outputs, res["tokens"], n_cols=lives[-1][2])
 
     prof = dom_only = e2e = None
-    if rank == 0 and not args.no_profile_pass:
+    if rank == 0 and args.full and not args.no_profile_pass:
         # pass 2: HIP events around every kernel class (eager launches) -> which class dominates, and the per-class table;
         # pass 3: events around the dominant class only, the rest of the step undisturbed -> its average launch duration
         nsync = lambda: torch.cuda.synchronize()
-        prof = run_pass(eng, reqs, cond, ff, args.warmup, args.steps, nsync, profile=True)
+        prof = run_pass(eng, reqs, cond, ff, args.warmup, last - first, nsync, profile=True)          # the first life's window
         tot = {k: v[0] * v[1] for k, v in prof["kern"].items()}
-        dom_only = run_pass(eng, reqs, cond, ff, args.warmup, args.steps, nsync, profile=True, only=max(tot, key=tot.get))
-    if rank == 0 and not args.no_e2e:
+        dom_only = run_pass(eng, reqs, cond, ff, args.warmup, last - first, nsync, profile=True, only=max(tot, key=tot.get))
+    if rank == 0 and args.full and not args.no_e2e:
         e2e = run_e2e(eng, reqs, cond)
     if use_dist:
         dist.barrier()
@@ -475,16 +541,16 @@ def main():
         out = dict(common)
         out.update({
             "value": round(value, 2), "ms_per_step": round(dt / args.steps * 1e3, 4),
-            "config": {"workload": workload_string(args, first, last),
+            "config": {"workload": workload_string(args, first, last, len(lives)), "windows": [[f, l] for _, f, l in lives],
                        "ctx_first": round(mean_T + first, 1), "ctx_last": round(mean_T + last - 1, 1),
-                       "fast_forward_steps": ff, "batch_per_gpu": args.batch, "global_batch": world * args.batch, "max_model_len": args.max_model_len,
+                       "fast_forward_steps": ff, "lives": len(lives), "batch_per_gpu": args.batch, "global_batch": world * args.batch, "max_model_len": args.max_model_len,
                        "layers": args.layers, "parallelism": f"dp{world} (utterance shards, no collective inside a step)",
                        "weights": "seeded synthetic N(0,0.02^2), seed 1234"},
             "tokens_per_s_per_gpu": round(value / world, 2),
             # in the timed window every utterance emits one token per step: its RTF there is the step time x 25.  The per-request figure
             # over whole utterances (prefill included) is e2e.rtf_p50 / rtf_p90.
             "rtf_p50": round((dt / args.steps) * S3_TOKEN_RATE, 5),
-            **step_percentiles(res["step_ms"]),
+            **step_percentiles(step_ms),
             "prefill_ms": round(res["prefill_s"] * 1e3, 2), "prefill_steps": res["prefill_steps"],
             "mean_ctx": round(st.sum_ctx_decode / st.decode_rows, 1),
             "step_roofline": {"bound": "hbm", "algo_bytes_per_step": round(bytes_step), "achieved": round(bytes_step / (dt / args.steps) / 1e9, 1),
@@ -494,8 +560,8 @@ def main():
             out["e2e"] = e2e
         if prof:
             out["roofline"], out["kernel_ms_per_step_all_classes_evented"] = dominant_kernel_roofline(prof, dom_only, args)   # eager + 2 events per kernel: over-reports
-            out["profiled_ms_per_step"] = round(prof["dt"] / args.steps * 1e3, 4)
-        if not args.no_cpu_baseline and world == 1:
+            out["profiled_ms_per_step"] = round(prof["dt"] / (last - first) * 1e3, 4)
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(weights, args)
         print(json.dumps(out), flush=True)
     if use_dist:

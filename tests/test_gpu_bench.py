@@ -29,7 +29,7 @@ CONTRACT_KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per
 
 
 def test_bench_two_ranks_gloo_rehearsal():
-    out = _bench(["--gpus", "2", "--steps", "5", "--warmup", "2", "--layers", "2", "--no-cpu-baseline", "--no-profile-pass"], {"T3_BENCH_BACKEND": "gloo"})
+    out = _bench(["--gpus", "2", "--steps", "5", "--warmup", "2", "--layers", "2", "--full", "--no-cpu-baseline", "--no-profile-pass"], {"T3_BENCH_BACKEND": "gloo"})
     assert CONTRACT_KEYS <= set(out)
     assert out["n_gpus"] == 2 and out["steps"] == 5 and out["warmup"] == 2 and out["scaling"] == "weak" and out["vs_baseline"] is None
     assert out["config"]["global_batch"] == 64 and out["config"]["batch_per_gpu"] == 32 and "dp2" in out["config"]["parallelism"]
@@ -45,6 +45,33 @@ def test_bench_one_rank_rccl_process_group():
     assert out["n_gpus"] == 1 and out["value"] > 0 and out["config"]["global_batch"] == 32
 
 
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without `--full` the line carries the window's figures only; `--dump-outputs` leaves the ids of the timed path as float32 arrays."""
+    import numpy as np
+    out = _bench(["--gpus", "1", "--steps", "5", "--warmup", "2", "--layers", "2", "--dump-outputs", str(tmp_path / "o")], {})
+    assert CONTRACT_KEYS <= set(out) and out["steps"] == 5 and out["value"] > 0
+    assert abs(out["value"] - 32 * 5 / (out["ms_per_step"] * 5e-3)) < 1e-2 * out["value"]
+    assert not {"e2e", "roofline", "cpu_baseline", "profiled_ms_per_step"} & set(out)
+    tok, last = np.load(tmp_path / "o" / "tokens.npy"), np.load(tmp_path / "o" / "last_step_tokens.npy")
+    n = int(out["config"]["fast_forward_steps"]) + 1 + 2 + 5             # the prefill step's token, then one per decode step
+    assert tok.dtype == np.float32 and tok.shape == (32, n) and last.dtype == np.float32 and np.array_equal(last, tok[:, -1])
+    assert (tok >= 2500).all() and (tok < 2500 + 8194).all() and (tok == np.floor(tok)).all()
+    assert len({tuple(r) for r in tok}) > 1                               # the utterances sample with their own counters
+
+
+def test_bench_times_more_steps_than_one_life_holds(tmp_path):
+    """max_model_len 200 leaves the 141-token prompt 56 decode steps: 120 timed steps after 2 warmup steps take three lives of the batch,
+    and the ids dumped from the last life (a 40-step window) are those a single-life run computes for the same decode steps."""
+    import numpy as np
+    common = ["--gpus", "1", "--warmup", "2", "--layers", "2", "--max-model-len", "200"]
+    out = _bench(common + ["--steps", "120", "--dump-outputs", str(tmp_path / "a")], {})
+    assert out["steps"] == 120 and out["config"]["lives"] == 3 and [l - f for f, l in out["config"]["windows"]] == [40, 40, 40]
+    assert abs(out["value"] - 32 * 120 / (out["ms_per_step"] * 120e-3)) < 1e-2 * out["value"] and out["step_ms_p50"] > 0
+    one = _bench(common + ["--steps", "40", "--dump-outputs", str(tmp_path / "b")], {})
+    assert one["config"]["lives"] == 1 and one["config"]["windows"] == out["config"]["windows"][-1:]
+    assert np.array_equal(np.load(tmp_path / "a" / "tokens.npy"), np.load(tmp_path / "b" / "tokens.npy"))
+
+
 def test_bench_c4_two_ranks():
     out = _bench(["--workload", "c4", "--gpus", "2", "--steps", "40", "--warmup", "5", "--layers", "2", "--no-cpu-baseline", "--no-profile-pass"],
                  {"T3_BENCH_BACKEND": "gloo"})
@@ -58,7 +85,7 @@ def test_bench_c4_two_ranks():
 def test_bench_c2_line_and_step_percentiles():
     """`--workload c2` = BASELINE.json configs[1] (English vocabulary 704, the T = 108 prompt, B = 1, max_model_len 400): the line a reader
     compares with the reference's only published number; every line carries the step-latency percentiles SURVEY.md 8(d) asks for."""
-    out = _bench(["--workload", "c2", "--steps", "30", "--warmup", "5", "--layers", "2", "--no-cpu-baseline"], {})
+    out = _bench(["--workload", "c2", "--steps", "30", "--warmup", "5", "--layers", "2", "--full", "--no-cpu-baseline"], {})
     assert CONTRACT_KEYS <= set(out) and out["config"]["workload"].startswith("custom")       # 2 layers: not the BASELINE config, and labelled so
     assert out["config"]["batch_per_gpu"] == 1 and out["config"]["max_model_len"] == 400 and "T=108" in out["config"]["workload"] and "vocab 704" in out["config"]["workload"]
     assert 0 < out["step_ms_p50"] <= out["step_ms_p90"] <= out["step_ms_p99"] <= out["step_ms_max"]

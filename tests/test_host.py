@@ -11,6 +11,8 @@ import torch
 
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# the reference's two tokenizer vocabulary files (t3/tokenizer.json, t3/grapheme_mtl_merged_expanded_v1.json), byte for byte
+EN_VOCAB, MTL_VOCAB = os.path.join(G, "vocab_en_tokenizer.json"), os.path.join(G, "vocab_grapheme_mtl_merged_expanded_v1.json")
 
 
 def test_prompt_assembly_layout():
@@ -27,29 +29,27 @@ def test_prompt_assembly_layout():
 
 
 def test_tokenizer_goldens():
-    """Token ids of the fixed utterances; the reference's tokenizer JSON files are read only if present."""
+    """Token ids of the fixed utterances, re-derived from the committed copies of the reference's vocabulary files."""
     tok = json.load(open(os.path.join(G, "tokenizer.json")))
     assert len(tok["en_english_ids"]) == 73 and tok["en_english_ids"][0] == 255 and tok["en_english_ids"][-1] == 0
     assert len(tok["en_mtl_ids"]) == 81 and len(tok["es_mtl_ids"]) == 106
     assert tok["en_mtl_ids"][0] == tok["lang"]["[en]"] == 708 and tok["es_mtl_ids"][0] == tok["lang"]["[es]"] == 635
     assert tok["special"] == {"[START]": 255, "[STOP]": 0, "[SPACE]": 2, "[UNK]": 1, "[PLACEHOLDER55]": 695, "[PLACEHOLDER56]": 696, "[PLACEHOLDER57]": 697}
     assert tok["en_vocab"] == 704 and tok["mtl_vocab"] == 2454
-    ref = "/root/reference/src/chatterbox_vllm/models/t3"
-    if os.path.exists(ref):        # build container only: re-derive from the reference's data files
-        from chatterbox_vllm2_amd.prompt import TextTokenizer
-        en = TextTokenizer("EnTokenizer", os.path.join(ref, "tokenizer.json"))
-        assert en.encode("[START]" + tok["en_text"] + "[STOP]") == tok["en_english_ids"]
-        mtl = TextTokenizer("MtlTokenizer", os.path.join(ref, "grapheme_mtl_merged_expanded_v1.json"))
-        assert mtl.encode("<es>[START]" + tok["es_text"] + "[STOP]") == tok["es_mtl_ids"]
-        # quirk: the multilingual path lower-cases the whole string, so [START]/[STOP] are NOT ids 255/0 there (SURVEY.md f2)
-        assert 255 not in tok["en_mtl_ids"]
+    from chatterbox_vllm2_amd.prompt import TextTokenizer
+    en = TextTokenizer("EnTokenizer", EN_VOCAB)
+    assert en.encode("[START]" + tok["en_text"] + "[STOP]") == tok["en_english_ids"]
+    mtl = TextTokenizer("MtlTokenizer", MTL_VOCAB)
+    assert mtl.encode("<es>[START]" + tok["es_text"] + "[STOP]") == tok["es_mtl_ids"]
+    # quirk: the multilingual path lower-cases the whole string, so [START]/[STOP] are NOT ids 255/0 there (SURVEY.md f2)
+    assert 255 not in tok["en_mtl_ids"]
 
 
 def test_tokenizer_matches_reference_classes():
     """prompt string -> ids.  tests/golden/tokenizer_cases.json holds the ids the reference's own
-    EnTokenizer / MTLTokenizer classes produced (make_golden.py g7b).  The vocabulary JSON files are the reference's data
-    and stay there, so the comparison itself runs where they are present (the build container); elsewhere only the
-    fixture's own invariants are checked.  zh / ja / he / ru normalisers need absent packages: parity unpinned for those."""
+    EnTokenizer / MTLTokenizer classes produced (make_golden.py g7b); the vocabulary JSON files those classes read are
+    committed beside it (tests/golden/vocab_*.json, the reference's data files unchanged), so the comparison runs everywhere.
+    zh / ja / he / ru normalisers need absent packages: parity unpinned for those."""
     cases = json.load(open(os.path.join(G, "tokenizer_cases.json")))
     assert len(cases["en"]) >= 10 and len(cases["mtl"]) >= 10
     for c in cases["en"]:
@@ -63,12 +63,9 @@ def test_tokenizer_matches_reference_classes():
         assert punc_norm(c["text"]) == c["out"], repr(c["text"])
     assert build_prompt_strings(["hi there"], "ES", multilingual=True) == ["<es>[START]Hi there.[STOP]"]      # tts.py:435-441
     assert build_prompt_strings(["hi there"]) == ["[START]Hi there.[STOP]"]
-    ref = "/root/reference/src/chatterbox_vllm/models/t3"
-    if not os.path.exists(ref):
-        pytest.skip("reference vocabulary files not present on this machine")
     from chatterbox_vllm2_amd.prompt import TextTokenizer
-    en = TextTokenizer("EnTokenizer", os.path.join(ref, "tokenizer.json"))
-    mtl = TextTokenizer("MtlTokenizer", os.path.join(ref, "grapheme_mtl_merged_expanded_v1.json"))
+    en = TextTokenizer("EnTokenizer", EN_VOCAB)
+    mtl = TextTokenizer("MtlTokenizer", MTL_VOCAB)
     for c in cases["en"]:
         assert en.encode(c["prompt"]) == c["ids"], c["prompt"]
     for c in cases["mtl"]:
@@ -137,11 +134,8 @@ def test_data_parallel_sharding_world2_gloo(tmp_path):
 
 def test_strict_tokenizer_refuses_unpinned_languages(tmp_path):
     """zh / ja / he / ru need normalisers (mtltokenizer.py:311-320) that cannot run here: refuse rather than emit other ids."""
-    ref = "/root/reference/src/chatterbox_vllm/models/t3/grapheme_mtl_merged_expanded_v1.json"
-    if not os.path.exists(ref):
-        pytest.skip("reference vocabulary file not present on this box")
     from chatterbox_vllm2_amd.prompt import TextTokenizer
-    strict, loose = TextTokenizer("MtlTokenizer", ref), TextTokenizer("MtlTokenizer", ref, strict=False)
+    strict, loose = TextTokenizer("MtlTokenizer", MTL_VOCAB), TextTokenizer("MtlTokenizer", MTL_VOCAB, strict=False)
     for lang in ("zh", "ja", "he", "ru"):
         with pytest.raises(ValueError):
             strict.encode(f"<{lang}>[START]x[STOP]")

@@ -5,7 +5,7 @@ usage: python tools/update_traffic.py profiles/<tag>_pmc_fetch_size_by_kernel.js
 For every kernel class bench.py can name as dominant: HBM bytes per launch = 2 * 1024 * FETCH_SIZE (KiB; gfx950 counts half of a wide
 coalesced stream, MI355X_MICROARCH.md "HBM"), the algorithmic bytes of the same launches, their ratio, and the sha256 of the kernel source
 the pass ran on -- bench.py applies the ratio only while that source is unchanged (otherwise roofline.traffic is null).
-The pass is `bench.py --steps 100 --warmup 5` on C3: its 64-row decode launches cover every decode step of the utterances' lives
+The pass is `bench.py --full --steps 100 --warmup 5` on C3: its 64-row decode launches cover every decode step of the utterances' lives
 (fast-forward + window + drain, twice with the e2e run), mean context 558.5 -> 558.5 x 64 rows x 4096 B algorithmic per attention launch."""
 import hashlib, json, os, sys
 
@@ -31,7 +31,7 @@ classes = {   # class -> (predicate on the kernel name of its 64-row decode form
     "gemm_down": (lambda n: n.startswith("gemm2_kernel<1, 1, 2, 16, 8, false, 8"), "t3_gemm.hip", 4096 * 1024 * 2 + 64 * 4096 * 2 + 2 * 64 * 1024 * 2),
     "gemm_o": (lambda n: n.startswith("gemm2_kernel<1, 1, 2, 16, 2, false, 2"), "t3_gemm.hip", 1024 * 1024 * 2 + 3 * 64 * 1024 * 2),
 }
-out = {"_how": "rocprofv3 --pmc FETCH_SIZE --kernel-trace (a pass of its own) -- python3 bench.py --steps 100 --warmup 5 --no-cpu-baseline --no-profile-pass "
+out = {"_how": "rocprofv3 --pmc FETCH_SIZE --kernel-trace (a pass of its own) -- python3 bench.py --full --steps 100 --warmup 5 --no-cpu-baseline --no-profile-pass "
                "(tools/run_profiles.sh), summarised on the box by tools/pmc_summarize.py, turned into this file by tools/update_traffic.py.  FETCH_SIZE is in KiB "
                "and counts HALF of a wide coalesced stream on gfx950 (MI355X_MICROARCH.md, HBM) -> bytes = 2 * 1024 * FETCH_SIZE; Infinity-Cache hits are counted too.",
        "_pass": os.path.relpath(src, ROOT)}
