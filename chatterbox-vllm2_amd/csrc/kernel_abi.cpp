@@ -147,8 +147,9 @@ extern "C" int t3k_silu_mul_gemm(const void* h, const void* ln_w, const void* wg
     return T3_OK;
 }
 
-extern "C" int t3k_rope_attention(const void* qkv, const int32_t* row_stream, const int32_t* row_pos, int32_t rows,
-                                  int32_t n_streams, int32_t max_pos, void* out) {
+// fp8: the same call over an FP8 (E4M3) pool -- one-byte elements, the FP8 launchers; kv_out (nullable) [rows][2][1024] = the stored K / V read back
+static int rope_attention_impl(const void* qkv, const int32_t* row_stream, const int32_t* row_pos, int32_t rows,
+                               int32_t n_streams, int32_t max_pos, void* out, bool fp8, void* kv_out) {
     if (!qkv || !row_stream || !row_pos || !out || rows <= 0 || n_streams <= 0 || max_pos <= 0) return T3_E_INVALID;
     if (!have_device()) return T3_E_DEVICE;
     for (int r = 0; r < rows; ++r)
@@ -175,14 +176,25 @@ extern "C" int t3k_rope_attention(const void* qkv, const int32_t* row_stream, co
     DevBuf dqkv, drec, dc, ds, dq, dkv, dout;
     K_TRY(dqkv.from(qkv, (size_t)rows * QKV * 2)); K_TRY(drec.from(recs.data(), recs.size() * 4));
     K_TRY(dc.from(c.data(), c.size() * 4)); K_TRY(ds.from(s.data(), s.size() * 4));
-    K_TRY(dq.alloc((size_t)rows * D * 2)); K_TRY(dkv.alloc((size_t)nb * KV_BLOCK_ELEMS * 2, true)); K_TRY(dout.alloc((size_t)rows * D * 2, true));
+    K_TRY(dq.alloc((size_t)rows * D * 2)); K_TRY(dkv.alloc((size_t)nb * KV_BLOCK_ELEMS * (fp8 ? 1 : 2), true)); K_TRY(dout.alloc((size_t)rows * D * 2, true));
     RopeArgs ra{dqkv.as<uint16_t>(), dq.as<uint16_t>(), dkv.as<uint16_t>(), drec.as<int>(), stride, dc.as<float>(), ds.as<float>(), rows};
-    K_TRY(launch_rope_kv(ra, nullptr));
+    K_TRY(fp8 ? launch_rope_kv_fp8(ra, nullptr) : launch_rope_kv(ra, nullptr));
     AttnArgs aa{dq.as<uint16_t>(), dkv.as<uint16_t>(), drec.as<int>(), stride, dout.as<uint16_t>(), rows, (max_pos + CHUNK - 1) / CHUNK, nullptr, nullptr, nullptr, nullptr, 0, 0};     // every row through the 16-row tile schedule
-    K_TRY(launch_attention(aa, nullptr));
+    K_TRY(fp8 ? launch_attention_fp8(aa, nullptr) : launch_attention(aa, nullptr));
+    DevBuf dkvo;
+    if (kv_out) { K_TRY(dkvo.alloc((size_t)rows * 2 * D * 2, true)); K_TRY(launch_kv_gather_fp8(dkv.as<uint16_t>(), drec.as<int>(), stride, rows, dkvo.as<uint16_t>(), nullptr)); }
     K_TRY(hipDeviceSynchronize());
     K_TRY(hipMemcpy(out, dout.p, (size_t)rows * D * 2, hipMemcpyDeviceToHost));
+    if (kv_out) K_TRY(hipMemcpy(kv_out, dkvo.p, (size_t)rows * 2 * D * 2, hipMemcpyDeviceToHost));
     return T3_OK;
+}
+extern "C" int t3k_rope_attention(const void* qkv, const int32_t* row_stream, const int32_t* row_pos, int32_t rows,
+                                  int32_t n_streams, int32_t max_pos, void* out) {
+    return rope_attention_impl(qkv, row_stream, row_pos, rows, n_streams, max_pos, out, false, nullptr);
+}
+extern "C" int t3k_rope_attention_fp8(const void* qkv, const int32_t* row_stream, const int32_t* row_pos, int32_t rows,
+                                      int32_t n_streams, int32_t max_pos, void* out, void* kv_out) {
+    return rope_attention_impl(qkv, row_stream, row_pos, rows, n_streams, max_pos, out, true, kv_out);
 }
 
 /* The FUSED decode attention exactly as a decode step launches it (attention_kernel<waves, nt, FUSE = true>: RoPE of q / k, paged
@@ -193,8 +205,8 @@ extern "C" int t3k_rope_attention(const void* qkv, const int32_t* row_stream, co
  *     reads the K / V that launch s - 1 wrote through the fused path.
  * out [steps][rows][1024]; kv_new (nullable) [steps][rows][2][1024]: K (rotated) and V of the positions the launches wrote, read
  * back from the pool. */
-extern "C" int t3k_decode_attention(const void* ctx_qkv, int32_t n_content, int32_t content_rows, const void* new_qkv, const int32_t* ctx,
-                                    int32_t rows, int32_t steps, int32_t max_pos, int32_t waves, void* out, void* kv_new) {
+static int decode_attention_impl(const void* ctx_qkv, int32_t n_content, int32_t content_rows, const void* new_qkv, const int32_t* ctx,
+                                 int32_t rows, int32_t steps, int32_t max_pos, int32_t waves, void* out, void* kv_new, bool fp8) {
     if (!ctx_qkv || !new_qkv || !ctx || !out || rows <= 0 || steps <= 0 || n_content <= 0 || content_rows <= 0 || max_pos <= 0 ||
         (waves != 0 && waves != 4 && waves != 8)) return T3_E_INVALID;
     for (int r = 0; r < rows; ++r)
@@ -215,7 +227,7 @@ extern "C" int t3k_decode_attention(const void* ctx_qkv, int32_t n_content, int3
     K_TRY(dctx.from(ctx_qkv, (size_t)n_content * content_rows * QKV * 2)); K_TRY(dnew.from(new_qkv, (size_t)steps * rows * QKV * 2));
     K_TRY(dc.from(c.data(), c.size() * 4)); K_TRY(ds.from(s.data(), s.size() * 4));
     K_TRY(dq.alloc((size_t)content_rows * D * 2));                     // rotated q of the fill rows: not used
-    K_TRY(dkv.alloc((size_t)nb * KV_BLOCK_ELEMS * 2, true)); K_TRY(dout.alloc((size_t)steps * rows * D * 2, true));
+    K_TRY(dkv.alloc((size_t)nb * KV_BLOCK_ELEMS * (fp8 ? 1 : 2), true)); K_TRY(dout.alloc((size_t)steps * rows * D * 2, true));
     K_TRY(dkvn.alloc((size_t)steps * rows * 2 * D * 2, true));
     // ---- context fill: one rope_kv launch per stream over its content's rows (positions 0 .. ctx[r] - 2)
     std::vector<int> recs((size_t)content_rows * stride);
@@ -232,7 +244,7 @@ extern "C" int t3k_decode_attention(const void* ctx_qkv, int32_t n_content, int3
         K_TRY(hipMemcpy(drec_fill.p, recs.data(), (size_t)n * stride * 4, hipMemcpyHostToDevice));
         RopeArgs ra{dctx.as<uint16_t>() + (size_t)(r % n_content) * content_rows * QKV, dq.as<uint16_t>(), dkv.as<uint16_t>(), drec_fill.as<int>(), stride,
                     dc.as<float>(), ds.as<float>(), n};
-        K_TRY(launch_rope_kv(ra, nullptr));
+        K_TRY(fp8 ? launch_rope_kv_fp8(ra, nullptr) : launch_rope_kv(ra, nullptr));
         K_TRY(hipDeviceSynchronize());                                 // the record buffer is reused by the next stream
     }
     // ---- the decode launches
@@ -248,13 +260,21 @@ extern "C" int t3k_decode_attention(const void* ctx_qkv, int32_t n_content, int3
         AttnArgs aa{nullptr, dkv.as<uint16_t>(), drec.as<int>(), stride, dout.as<uint16_t>() + (size_t)st * rows * D, rows, (max_pos + CHUNK - 1) / CHUNK,
                     dnew.as<uint16_t>() + (size_t)st * rows * QKV, dkv.as<uint16_t>(), dc.as<float>(), ds.as<float>()};
         aa.force_waves = waves;
-        K_TRY(launch_attention(aa, nullptr));
-        K_TRY(launch_kv_gather(dkv.as<uint16_t>(), drec.as<int>(), stride, rows, dkvn.as<uint16_t>() + (size_t)st * rows * 2 * D, nullptr));
+        K_TRY(fp8 ? launch_attention_fp8(aa, nullptr) : launch_attention(aa, nullptr));
+        K_TRY((fp8 ? launch_kv_gather_fp8 : launch_kv_gather)(dkv.as<uint16_t>(), drec.as<int>(), stride, rows, dkvn.as<uint16_t>() + (size_t)st * rows * 2 * D, nullptr));
         K_TRY(hipDeviceSynchronize());
     }
     K_TRY(hipMemcpy(out, dout.p, (size_t)steps * rows * D * 2, hipMemcpyDeviceToHost));
     if (kv_new) K_TRY(hipMemcpy(kv_new, dkvn.p, (size_t)steps * rows * 2 * D * 2, hipMemcpyDeviceToHost));
     return T3_OK;
+}
+extern "C" int t3k_decode_attention(const void* ctx_qkv, int32_t n_content, int32_t content_rows, const void* new_qkv, const int32_t* ctx,
+                                    int32_t rows, int32_t steps, int32_t max_pos, int32_t waves, void* out, void* kv_new) {
+    return decode_attention_impl(ctx_qkv, n_content, content_rows, new_qkv, ctx, rows, steps, max_pos, waves, out, kv_new, false);
+}
+extern "C" int t3k_decode_attention_fp8(const void* ctx_qkv, int32_t n_content, int32_t content_rows, const void* new_qkv, const int32_t* ctx,
+                                        int32_t rows, int32_t steps, int32_t max_pos, int32_t waves, void* out, void* kv_new) {
+    return decode_attention_impl(ctx_qkv, n_content, content_rows, new_qkv, ctx, rows, steps, max_pos, waves, out, kv_new, true);
 }
 
 static int sample_impl(const void* logits2, int32_t ldl, uint16_t* counts, const T3Sampling* sp, float cfg, uint32_t step,
@@ -302,6 +322,17 @@ extern "C" int t3k_handoff(const int32_t* ids, int32_t n, int32_t text_token_cou
     K_TRY(hipDeviceSynchronize());
     K_TRY(hipMemcpy(out, dout.p, (size_t)ld * 4, hipMemcpyDeviceToHost));
     K_TRY(hipMemcpy(len, dlen.p, 4, hipMemcpyDeviceToHost));
+    return T3_OK;
+}
+
+extern "C" int t3k_fp8_roundtrip(const float* x, float* y, int32_t n) {
+    if (!x || !y || n <= 0) return T3_E_INVALID;
+    if (!have_device()) return T3_E_DEVICE;
+    DevBuf dx, dy;
+    K_TRY(dx.from(x, (size_t)n * 4)); K_TRY(dy.alloc((size_t)n * 4));
+    K_TRY(launch_fp8_roundtrip(dx.as<float>(), dy.as<float>(), n, nullptr));
+    K_TRY(hipDeviceSynchronize());
+    K_TRY(hipMemcpy(y, dy.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     return T3_OK;
 }
 

@@ -119,6 +119,12 @@ struct AttnArgs {
 hipError_t launch_attention(const AttnArgs& a, hipStream_t s);
 // parity hook: K (as stored, i.e. rotated) and V of every row's (stream, position) read back from the paged pool -> out [rows][2][1024]
 hipError_t launch_kv_gather(const uint16_t* kv_layer, const int* rowrec, int row_stride, int rows, uint16_t* out, hipStream_t s);
+// The same three over an FP8 (E4M3FN) pool, t3_attention_fp8.hip (T3EngineConfig.kv_cache_dtype = 1): same argument structs, but kv_layer /
+// kv_layer_w point at ONE-byte elements (a layer of the pool is n_blocks * KV_BLOCK_ELEMS bytes); the gather dequantises to bf16.
+hipError_t launch_rope_kv_fp8(const RopeArgs& a, hipStream_t s);
+hipError_t launch_attention_fp8(const AttnArgs& a, hipStream_t s);
+hipError_t launch_kv_gather_fp8(const uint16_t* kv_layer, const int* rowrec, int row_stride, int rows, uint16_t* out, hipStream_t s);
+hipError_t launch_fp8_roundtrip(const float* x, float* y, int n, hipStream_t s);   // parity hook: y = dequantised q8(x)
 
 struct SampleArgs {
     const uint16_t* logits;    // [2*n][ldl] bf16: row 2i cond, 2i+1 uncond

@@ -27,7 +27,7 @@ class T3EngineConfig(ct.Structure):
         ("device_id", ct.c_int32), ("n_layers", ct.c_int32), ("text_vocab", ct.c_int32),
         ("max_model_len", ct.c_int32), ("max_seqs", ct.c_int32), ("max_batched_rows", ct.c_int32),
         ("kv_bytes", ct.c_int64), ("gpu_memory_utilization", ct.c_float), ("cfg_scale", ct.c_float),
-        ("enforce_eager", ct.c_int32), ("debug_logits", ct.c_int32), ("n_groups", ct.c_int32), ("_pad", ct.c_int32),
+        ("enforce_eager", ct.c_int32), ("debug_logits", ct.c_int32), ("n_groups", ct.c_int32), ("kv_cache_dtype", ct.c_int32),
     ]
 
 
@@ -63,6 +63,7 @@ ABI_SYMBOLS = [
     "t3_step", "t3_run_until_done", "t3_run_steps", "t3_num_unfinished", "t3_get_output", "t3_get_timing", "t3_release_request", "t3_abort_request", "t3_handoff_tokens", "t3_reserve_handoff", "t3_pop_finished", "t3_debug_embeddings", "t3k_handoff",
     "t3_clean_tokens", "t3_debug_logits", "t3_step_times", "t3_stats", "t3_reset_stats", "t3_set_profile", "t3_set_profile_kernel", "t3_kernel_ms",
     "t3k_gemm", "t3k_norm_gemm", "t3k_qkv_gemm", "t3k_head_gemm", "t3k_gemm_resid", "t3k_silu_mul_gemm", "t3k_rope_attention", "t3k_decode_attention", "t3k_sample", "t3k_sample_support", "t3k_expf",
+    "t3k_fp8_roundtrip", "t3k_rope_attention_fp8", "t3k_decode_attention_fp8",
     "t3_cond_create", "t3_cond_destroy", "t3_cond_last_error", "t3_cond_load_tensor", "t3_cond_encode", "t3_cond_emotion_row",
     "t3k_ce_layernorm", "t3k_ce_linear", "t3k_ce_attention", "t3k_set_prefill_rows", "t3k_set_prefill_wide_rows",
 ]
@@ -129,6 +130,9 @@ def load_library():
     L.t3k_sample.argtypes = [vp, i32, vp, ct.POINTER(T3Sampling), ct.c_float, ct.c_uint32, vp, vp]
     L.t3k_sample_support.argtypes = [vp, i32, vp, ct.POINTER(T3Sampling), ct.c_float, ct.c_uint32, vp, vp]
     L.t3k_expf.argtypes = [vp, vp, i32]
+    L.t3k_fp8_roundtrip.argtypes = [vp, vp, i32]
+    L.t3k_rope_attention_fp8.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
+    L.t3k_decode_attention_fp8.argtypes = [vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp]
     L.t3_cond_create.argtypes = [i32, ct.POINTER(vp)]
     L.t3_cond_destroy.argtypes = [vp]
     L.t3_cond_last_error.restype = ct.c_char_p; L.t3_cond_last_error.argtypes = [vp]
@@ -168,19 +172,33 @@ def make_sampling(temperature=0.8, top_p=1.0, min_p=0.0, repetition_penalty=2.0,
                       int(bool(ignore_eos)), int(stop_token), int(seed), int(uid), int(pos_policy), 0)
 
 
+# storage formats of the paged KV pool (T3EngineConfig.kv_cache_dtype), under vLLM's names for them
+KV_CACHE_DTYPES = {"auto": 0, "bfloat16": 0, "bf16": 0, "fp8": 1, "fp8_e4m3": 1}
+
+
+def kv_cache_dtype_code(name) -> int:
+    """vLLM's kv_cache_dtype strings -> T3EngineConfig.kv_cache_dtype; None = the T3_KV_CACHE_DTYPE environment variable, else bf16."""
+    if name is None:
+        name = os.environ.get("T3_KV_CACHE_DTYPE", "bf16")
+    if name not in KV_CACHE_DTYPES:
+        raise ValueError(f"kv_cache_dtype {name!r}: the T3 engine stores bf16 ('auto', 'bfloat16') or FP8 E4M3 ('fp8', 'fp8_e4m3')")
+    return KV_CACHE_DTYPES[name]
+
+
 class T3Engine:
     """Thin object wrapper over one engine handle (one GPU)."""
 
     def __init__(self, n_layers: int = C.N_LAYERS, text_vocab: int = C.TEXT_VOCAB_EN, max_model_len: int = 1000,
                  max_seqs: int = 32, device_id: int = 0, kv_bytes: int = 0, gpu_memory_utilization: float = 0.9,
                  cfg_scale: Optional[float] = None, enforce_eager: bool = True, debug_logits: bool = False,
-                 max_batched_rows: int = 0, n_groups: int = 0):
+                 max_batched_rows: int = 0, n_groups: int = 0, kv_cache_dtype: Optional[str] = None):
+        kv_code = kv_cache_dtype_code(kv_cache_dtype)
         self.lib = load_library()
         if cfg_scale is None:
             cfg_scale = float(os.environ.get("CHATTERBOX_CFG_SCALE", "0.5"))   # t3.py:296
         self.cfg = T3EngineConfig(device_id, n_layers, text_vocab, max_model_len, max_seqs, max_batched_rows,
                                   int(kv_bytes), float(gpu_memory_utilization), float(cfg_scale),
-                                  int(enforce_eager), int(debug_logits), int(n_groups), 0)
+                                  int(enforce_eager), int(debug_logits), int(n_groups), kv_code)
         self.h = ct.c_void_p()
         rc = self.lib.t3_create(ct.byref(self.cfg), ct.byref(self.h))
         if rc:
@@ -426,6 +444,36 @@ def k_decode_attention(ctx_qkv: torch.Tensor, new_qkv: torch.Tensor, ctx, max_po
     out = torch.empty(steps, rows, C.HIDDEN, dtype=torch.bfloat16); kvn = torch.empty(steps, rows, 2, C.HIDDEN, dtype=torch.bfloat16)
     _chk_k(load_library().t3k_decode_attention(ctx_qkv.data_ptr(), ctx_qkv.shape[0], ctx_qkv.shape[1], new_qkv.data_ptr(), cx.ctypes.data,
                                                rows, steps, int(max_pos), int(waves), out.data_ptr(), kvn.data_ptr()), "t3k_decode_attention")
+    return out, kvn
+
+
+def k_fp8_roundtrip(x: torch.Tensor) -> torch.Tensor:
+    """q8 on the device and back: the stored format of the FP8 KV pool (fp32 in, fp32 out)."""
+    x = x.to(torch.float32).contiguous()
+    y = torch.empty_like(x)
+    _chk_k(load_library().t3k_fp8_roundtrip(x.data_ptr(), y.data_ptr(), x.numel()), "t3k_fp8_roundtrip")
+    return y
+
+
+def k_rope_attention_fp8(qkv: torch.Tensor, row_stream, row_pos, n_streams: int, max_pos: int):
+    """k_rope_attention over an FP8 pool -> (out [rows, 1024] bf16, stored K / V of every row's position, dequantised [rows, 2, 1024] bf16)"""
+    qkv = _bf(qkv)
+    rs = np.ascontiguousarray(np.asarray(row_stream, dtype=np.int32)); rp = np.ascontiguousarray(np.asarray(row_pos, dtype=np.int32))
+    out = torch.empty(qkv.shape[0], C.HIDDEN, dtype=torch.bfloat16); kvo = torch.empty(qkv.shape[0], 2, C.HIDDEN, dtype=torch.bfloat16)
+    _chk_k(load_library().t3k_rope_attention_fp8(qkv.data_ptr(), rs.ctypes.data, rp.ctypes.data, qkv.shape[0], n_streams, max_pos,
+                                                 out.data_ptr(), kvo.data_ptr()), "t3k_rope_attention_fp8")
+    return out, kvo
+
+
+def k_decode_attention_fp8(ctx_qkv: torch.Tensor, new_qkv: torch.Tensor, ctx, max_pos: int, waves: int = 0):
+    """k_decode_attention over an FP8 pool: same arguments, kv_new read back dequantised."""
+    ctx_qkv, new_qkv = _bf(ctx_qkv), _bf(new_qkv)
+    cx = np.ascontiguousarray(np.asarray(ctx, dtype=np.int32))
+    steps, rows = new_qkv.shape[0], new_qkv.shape[1]
+    assert ctx_qkv.dim() == 3 and ctx_qkv.shape[2] == 3072 and new_qkv.shape[2] == 3072 and len(cx) == rows
+    out = torch.empty(steps, rows, C.HIDDEN, dtype=torch.bfloat16); kvn = torch.empty(steps, rows, 2, C.HIDDEN, dtype=torch.bfloat16)
+    _chk_k(load_library().t3k_decode_attention_fp8(ctx_qkv.data_ptr(), ctx_qkv.shape[0], ctx_qkv.shape[1], new_qkv.data_ptr(), cx.ctypes.data,
+                                                   rows, steps, int(max_pos), int(waves), out.data_ptr(), kvn.data_ptr()), "t3k_decode_attention_fp8")
     return out, kvn
 
 

@@ -20,7 +20,7 @@ from typing import Any, Dict, List, Optional, Sequence, Union
 import torch
 
 from . import constants as C
-from .engine import T3Engine, make_sampling
+from .engine import T3Engine, kv_cache_dtype_code, make_sampling
 from .prompt import TextTokenizer, assemble_prompt_ids, find_tokenizer_file
 from .weights import iter_safetensors, synthetic_tensors
 
@@ -96,11 +96,15 @@ class LLM:
                  enforce_eager: bool = True, max_model_len: int = 1000, max_num_seqs: int = 256,
                  max_num_batched_tokens: int = 0, seed: int = 0, load_format: str = "auto", dtype: str = "bfloat16",
                  device_id: Optional[int] = None, tokenizer_file: Optional[str] = None, num_hidden_layers: Optional[int] = None,
-                 kv_cache_bytes: int = 0, debug_logits: bool = False, honor_enforce_eager: Optional[bool] = None, **kwargs):
+                 kv_cache_bytes: int = 0, debug_logits: bool = False, honor_enforce_eager: Optional[bool] = None,
+                 kv_cache_dtype: Optional[str] = None, **kwargs):
         if task != "generate":
             raise ValueError("only task='generate' exists on the T3 path")
         if dtype not in ("bfloat16", "auto", torch.bfloat16):
             raise ValueError("the T3 engine computes in bf16 storage / fp32 accumulation only")
+        # vLLM's switch for the storage format of the KV cache ("auto" / "bfloat16": bf16; "fp8" / "fp8_e4m3": E4M3 with scale 1.0, half
+        # the bytes per token; anything else, "fp8_e5m2" included, is a ValueError).  None: the T3_KV_CACHE_DTYPE environment variable.
+        kv_cache_dtype_code(kv_cache_dtype)
         for k in kwargs:
             warnings.warn(f"LLM(...) keyword {k!r} has no meaning for the T3 engine and is ignored")
         self.model_dir = model
@@ -124,7 +128,8 @@ class LLM:
         eager = bool(enforce_eager) and self.honor_enforce_eager
         self.engine = T3Engine(n_layers=n_layers, text_vocab=text_vocab, max_model_len=max_model_len, max_seqs=max_num_seqs,
                                device_id=device_id, kv_bytes=kv_cache_bytes, gpu_memory_utilization=gpu_memory_utilization,
-                               enforce_eager=eager, debug_logits=debug_logits, max_batched_rows=max_num_batched_tokens)
+                               enforce_eager=eager, debug_logits=debug_logits, max_batched_rows=max_num_batched_tokens,
+                               kv_cache_dtype=kv_cache_dtype)
         ckpt = os.path.join(model, "model.safetensors") if model and os.path.isdir(model) else model
         if load_format == "dummy" or not (ckpt and os.path.exists(ckpt)):
             if load_format != "dummy":

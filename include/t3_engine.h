@@ -52,7 +52,9 @@ typedef struct {
     int32_t enforce_eager;     /* 1: never use hipGraph replay (tts.py:163) */
     int32_t debug_logits;      /* 1: keep post-CFG logits of each sampled step for t3_debug_logits */
     int32_t n_groups;          /* utterance groups run concurrently on separate HIP streams; 0 = auto */
-    int32_t _pad;
+    int32_t kv_cache_dtype;    /* storage format of the paged KV pool: 0 = bf16 (default), 1 = FP8 E4M3FN with scale 1.0 (vLLM's
+                                  kv_cache_dtype="fp8": half the bytes per token); any other value is T3_E_INVALID.  This was padding:
+                                  a C caller must zero it */
 } T3EngineConfig;
 
 /* Replaces vllm.SamplingParams as configured at tts.py:455-464 (+ the kwargs it forwards). */
@@ -268,6 +270,15 @@ int t3k_sample(const void* logits2_bf16, int32_t ldl, uint16_t* counts, const T3
 int t3k_sample_support(const void* logits2_bf16, int32_t ldl, uint16_t* counts, const T3Sampling* sp, float cfg,
                        uint32_t step, int32_t* token_out, uint8_t* keep_out_8194);
 int t3k_expf(const float* x, float* y, int32_t n);
+/* ---- the FP8 (E4M3FN) KV pool, kv_cache_dtype = 1 ----
+ * y = dequantised q8(x) on the device, q8(x) = e4m3fn(round-to-nearest-even(clamp(x, -448, 448))): the stored format of the FP8 pool. */
+int t3k_fp8_roundtrip(const float* x, float* y, int32_t n);
+/* t3k_rope_attention over an FP8 pool; kv_bf16 (nullable) [rows][2][1024] = the stored K (rotated) and V of every row's position, dequantised. */
+int t3k_rope_attention_fp8(const void* qkv_bf16, const int32_t* row_stream, const int32_t* row_pos, int32_t rows,
+                           int32_t n_streams, int32_t max_pos, void* out_bf16, void* kv_bf16);
+/* t3k_decode_attention over an FP8 pool: same arguments and meaning, kv_new read back dequantised. */
+int t3k_decode_attention_fp8(const void* ctx_qkv_bf16, int32_t n_content, int32_t content_rows, const void* new_qkv_bf16, const int32_t* ctx,
+                             int32_t rows, int32_t steps, int32_t max_pos, int32_t waves, void* out_bf16, void* kv_new_bf16);
 /* the hand-off kernel on host buffers (one utterance): out [ld] padded with 0, *len = kept tokens */
 int t3k_handoff(const int32_t* speech_ids, int32_t n, int32_t text_token_count, int32_t flags, int32_t* out, int32_t ld, int32_t* len);
 /* Row count from which the GEMM launcher switches to its prefill schedule (same numbers, LDS-tiled); process-wide.
