@@ -58,6 +58,8 @@ struct Request {
     int n_seen = 0;                   // sampled results read back (kept or, once finished, dropped): == n_sched when nothing of it is in flight
     bool zombie = false;
     int32_t* d_out = nullptr;         // finished: the utterance's speech-space ids on the device (f4 hand-off), from the engine's buffer pool
+    float* d_align = nullptr;         // finished, sp.alignment: its rows of the slot's alignment frames [out.size()][align_ld], a buffer of its own
+    int align_ld = 0;                 // ... with the row pitch of the reserve it ran under
     double t_add = 0, t_admit = 0, t_first = 0, t_finish = 0;     // seconds since the engine was created (t3_get_timing)
 };
 
@@ -118,11 +120,12 @@ struct T3Engine {
         uint64_t waited_admit_seq = 0;     // the admission this group's stream has been ordered behind
         hipEvent_t ev_done[NBUF] = {};
         int rcap = 0;              // row budget per step
-        std::map<std::tuple<int, int, int, int>, hipGraphExec_t> graphs;   // (M, n_sel, first staging buffer, steps) -> captured decode step(s)
+        std::map<std::tuple<int, int, int, int, bool>, hipGraphExec_t> graphs;   // (M, n_sel, first staging buffer, steps, tapped) -> captured decode step(s)
     };
     // One enqueued step: what the scheduler put on each group's stream, kept until its tokens are back.
     struct StepRec {
         int M = 0, n_sel = 0, n_prefill_rows = 0, decode_rows = 0;
+        bool tapped = false;           // a sampled row of the step feeds the alignment export: the tap launches follow their layers' attention
         int max_prefill_ctx = 0;       // longest context among the step's prefill rows (sizes the tile attention's LDS)
         double sum_ctx = 0;
         std::vector<Request*> sampled;
@@ -156,6 +159,12 @@ struct T3Engine {
     std::vector<void*> out_slabs;      // the allocations the pool was carved from
     HandoffItem* d_handoff_items = nullptr; int handoff_items_cap = 0;      // persistent argument buffer of t3_handoff_tokens
     hipEvent_t ev_handoff = nullptr;
+    // alignment export (t3_reserve_alignment): per slot [max_model_len frames][align_ld] fp32, row k = what the taps' heads pay to the text
+    // positions while token k is drawn (t3_alignment.hip).  Rows are align_ld = max_text rounded up to 4 floats apart.
+    float* d_align = nullptr; int align_max_text = 0, align_ld = 0;
+    std::vector<float*> align_pool;    // free per-request matrix buffers of the current reserve (max_model_len x align_ld each): a finished request
+                                       // takes one, its release gives it back, so a steady serving loop neither allocates nor frees inside the step loop
+    int taps[4][2] = {}; int n_taps = 0;    // (layer, head), layers strictly ascending
     std::deque<int64_t> finished_q;    // ids finished since the last t3_pop_finished (T3StepResult carries only the first 64 of a step)
     uint16_t* d_dbg_emb = nullptr;     // debug_logits: the embedded input rows of the most recent step (t3_debug_embeddings)
     std::vector<int> dbg_emb_rec;      // their (stream, position) pairs
@@ -213,6 +222,10 @@ extern "C" int t3_create(const T3EngineConfig* cfg, T3Handle* out) {
     e->rmax = cfg->max_batched_rows > 0 ? cfg->max_batched_rows : std::max(2048, 2 * cfg->max_seqs);
     e->rmax = std::max(e->rmax, 2 * cfg->max_seqs);
     e->slot_req.assign(cfg->max_seqs, -1);
+    {   // the reference's LLAMA_ALIGNED_HEADS [(12, 15), (13, 11), (9, 2)] in layer order, as far as the layers exist
+        const int def[3][2] = {{9, 2}, {12, 15}, {13, 11}};
+        for (auto& t : def) if (t[0] < cfg->n_layers) { e->taps[e->n_taps][0] = t[0]; e->taps[e->n_taps][1] = t[1]; ++e->n_taps; }
+    }
     {
         int g = cfg->n_groups > 0 ? cfg->n_groups : 1;   // measured on MI355X/ROCm 7.2: kernels of different streams do not overlap usefully (2 groups +0 %, 4 groups -60 %)
         if (const char* ev = getenv("T3_GROUPS")) g = atoi(ev);
@@ -260,6 +273,9 @@ extern "C" int t3_destroy(T3Handle e) {
     free_dev(e->d_cond); free_dev(e->d_counts); free_dev(e->d_sp); free_dev(e->d_dbg); free_dev(e->d_hist);
     for (void* b : e->out_slabs) free_dev(b);      // every hand-off buffer (pooled or held by a request) lives in one of these
     free_dev(e->d_handoff_items); free_dev(e->d_dbg_emb);
+    free_dev(e->d_align);
+    for (float* b : e->align_pool) free_dev(b);
+    for (auto& kv : e->reqs) free_dev(kv.second.d_align);
     if (e->ev_handoff) (void)hipEventDestroy(e->ev_handoff);
     if (e->ev_admit) (void)hipEventDestroy(e->ev_admit);
     for (int k = 0; k < K_COUNT; ++k) for (auto& p : e->pev[k]) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
@@ -491,6 +507,13 @@ extern "C" int t3_add_request(T3Handle e, int64_t req_id, const int32_t* ids, in
         uint32_t u; memcpy(&u, cond + i, 4);
         if ((u & 0x7f800000u) == 0x7f800000u) return e->fail(T3_E_INVALID, "conditioning embedding contains a non-finite value");
     }
+    if (sp->alignment != 0 && sp->alignment != 1) return e->fail(T3_E_INVALID, "T3Sampling.alignment must be 0 or 1");
+    if (sp->alignment) {
+        if (!e->d_align) return e->fail(T3_E_STATE, "alignment export asked for before t3_reserve_alignment");
+        if (e->n_taps == 0) return e->fail(T3_E_STATE, "no alignment head: none of the default taps' layers exists and t3_set_alignment_heads was not called");
+        if (T - 1 - T3_COND_ROWS > e->align_max_text)
+            return e->fail(T3_E_INVALID, "alignment export: " + std::to_string(T - 1 - T3_COND_ROWS) + " text tokens exceed the reserved " + std::to_string(e->align_max_text));
+    }
     Request r;
     r.id = req_id; r.prompt.assign(ids, ids + T); r.cond.assign(cond, cond + (size_t)T3_COND_ROWS * D); r.sp = *sp;
     r.limit = std::min(sp->max_tokens, e->cfg.max_model_len - T);
@@ -502,6 +525,23 @@ extern "C" int t3_add_request(T3Handle e, int64_t req_id, const int32_t* ids, in
 
 extern "C" int t3_num_unfinished(T3Handle e) { return e ? (int)(e->waiting.size() + e->running.size()) : 0; }
 
+// a finished request's alignment matrix goes back to the pool (a buffer of an earlier reserve, with another pitch, is freed)
+static void release_align(T3Engine* e, Request& r) {
+    if (!r.d_align) return;
+    if (e->d_align && r.align_ld == e->align_ld) e->align_pool.push_back(r.d_align);
+    else { (void)hipSetDevice(e->cfg.device_id); (void)hipFree(r.d_align); }
+    r.d_align = nullptr;
+}
+// The captured decode steps bake in what the tap launches were given (the frame buffer, its pitch, the heads and which layers carry a tap):
+// whatever changes one of those drops them.  The caller has made sure nothing is queued or running.
+static int drop_graphs(T3Engine* e) {
+    for (auto& g : e->groups) {
+        if (g.stream) HIP_TRY(hipStreamSynchronize(g.stream));      // a replay, or a finished request's copy-out, may still be running
+        for (auto& kv : g.graphs) (void)hipGraphExecDestroy(kv.second);
+        g.graphs.clear();
+    }
+    return T3_OK;
+}
 static void release_slot(T3Engine* e, Request& r) {
     for (int s = 0; s < 2; ++s) { for (int b : r.blocks[s]) e->free_blocks.push_back(b); r.blocks[s].clear(); }
     if (r.slot >= 0) e->slot_req[r.slot] = -1;
@@ -530,6 +570,11 @@ static int admit(T3Engine* e) {
         HIP_TRY(hipMemcpyAsync(e->d_cond + (size_t)slot * T3_COND_ROWS * D, r.cond.data(), (size_t)T3_COND_ROWS * D * 4, hipMemcpyHostToDevice, e->stream));
         HIP_TRY(hipMemsetAsync(e->d_counts + (size_t)slot * VPAD, 0, VPAD * 2, e->stream));
         HIP_TRY(hipMemcpyAsync(e->d_sp + slot, &r.sp, sizeof(T3Sampling), hipMemcpyHostToDevice, e->stream));
+        // The slot's alignment frames start at zero.  Not needed for the result -- the first tap stores every frame that is copied out -- but a zero
+        // row in a returned matrix then means a frame nobody wrote (what the tests look for), at 1.4-5 us per tapped request.  On the slot's GROUP
+        // stream, not the admission stream: the previous occupant's copy-out (complete_step) was queued there, and the clear must stay behind it.
+        if (r.sp.alignment)
+            HIP_TRY(launch_alignment_clear(e->d_align + (size_t)slot * e->cfg.max_model_len * e->align_ld, (size_t)r.limit * e->align_ld, e->groups[slot % e->n_groups].stream));
         // r.cond / r.sp are kept alive in the request map until the copy is consumed (stream-ordered, pageable -> staged synchronously)
         e->running.push_back(r.id);
     }
@@ -607,6 +652,16 @@ static int launch_attention_phase(T3Engine* e, T3Engine::Group& g, const T3Engin
     }
     return T3_OK;
 }
+// The alignment taps of layer L, directly behind its attention: the pool holds the rows' newest K and the step's qkv buffer is still intact.
+static int launch_alignment_phase(T3Engine* e, T3Engine::Group& g, const T3Engine::StepRec& sr, int L, hipStream_t s) {
+    for (int t = 0; t < e->n_taps; ++t) {
+        if (e->taps[t][0] != L) continue;
+        AlignArgs a{g.qkv, e->kv + (size_t)L * e->n_blocks * KV_BLOCK_ELEMS * e->kv_esz, g.dm.rows, e->row_stride, g.dm.sel_rows, e->cos_t, e->sin_t, e->d_align,
+                    sr.n_sel, e->taps[t][1], T3_COND_ROWS, (e->cfg.max_model_len + CHUNK - 1) / CHUNK, e->cfg.max_model_len, e->align_ld, t, e->n_taps, 1.0f / (float)e->n_taps};
+        HIP_TRY(launch_alignment(a, e->kv_esz == 1, s));
+    }
+    return T3_OK;
+}
 static int launch_mlp_phase(T3Engine* e, T3Engine::Group& g, const T3Engine::StepRec& sr, int L, hipStream_t s) {
     LayerW& y = e->layers[L];
     const int M = sr.M;
@@ -639,6 +694,7 @@ static int launch_step(T3Engine* e, T3Engine::Group& g, const T3Engine::StepRec&
     for (int L = 0; L < e->cfg.n_layers; ++L) {
         if ((rc = launch_qkv_phase(e, g, sr, L, s))) return rc;
         if ((rc = launch_attention_phase(e, g, sr, L, s))) return rc;
+        if (sr.tapped && (rc = launch_alignment_phase(e, g, sr, L, s))) return rc;
         if ((rc = launch_mlp_phase(e, g, sr, L, s))) return rc;
     }
     return launch_sample_phase(e, g, sr, buf, s);
@@ -656,9 +712,14 @@ static int build_step(T3Engine* e, T3Engine::Step& st, bool may_admit) {
     auto add_row = [&](int gi, int stream, int pos, int kind, int a, int b) {
         T3Engine::StepRec& sr = st.g[gi];
         int* rec = e->groups[gi].hm[buf].rows + (size_t)sr.M * e->row_stride;
-        rec[0] = stream; rec[1] = pos; rec[2] = kind; rec[3] = a; rec[4] = b;
+        rec[0] = stream; rec[1] = pos; rec[2] = kind; rec[3] = a; rec[4] = b; rec[ROW_ALIGN_FRAME] = -1;
         memcpy(rec + ROW_HDR, &e->h_block_table[(size_t)stream * e->max_blocks], (size_t)e->max_blocks * 4);
         ++sr.M;
+    };
+    auto tap_row = [&](int gi, int frame, int n_text) {      // the row just added is a tapped request's conditional sampled row
+        T3Engine::StepRec& sr = st.g[gi];
+        int* rec = e->groups[gi].hm[buf].rows + (size_t)(sr.M - 1) * e->row_stride;
+        rec[ROW_ALIGN_FRAME] = frame; rec[ROW_ALIGN_NTEXT] = n_text; sr.tapped = true;
     };
     // decode rows of every running utterance, then prefill rows within the group's budget.  Longest context first: the fused attention's
     // workgroups (one per row and head, dispatched in row order) take a time proportional to the row's context, and a long row handed out
@@ -683,6 +744,7 @@ static int build_step(T3Engine* e, T3Engine::Step& st, bool may_admit) {
         const bool known = (int)r.out.size() == n;
         const int kind = known ? EMB_SPEECH : EMB_SPEECH_PREV, a = known ? r.out.back() : r.last_idx;
         hm.sel_rows[2 * sr.n_sel] = sr.M;     add_row(gi, 2 * r.slot, pos, kind, a, spos);
+        if (r.sp.alignment) tap_row(gi, n, T - 1 - T3_COND_ROWS);      // this row's logits draw token n
         hm.sel_rows[2 * sr.n_sel + 1] = sr.M; add_row(gi, 2 * r.slot + 1, pos, kind, a, spos);
         hm.sel[sr.n_sel] = make_int4(r.slot, n, 0, 0);
         sr.sum_ctx += 2.0 * (pos + 1);
@@ -706,6 +768,7 @@ static int build_step(T3Engine* e, T3Engine::Step& st, bool may_admit) {
                 else if (p < T - 1) { if (sI == 0) add_row(gi, 2 * r.slot, p, EMB_TEXT, r.prompt[p], p - T3_COND_ROWS); else add_row(gi, 2 * r.slot + 1, p, EMB_ZERO, 0, 0); }
                 else add_row(gi, 2 * r.slot + sI, p, EMB_SPEECH, 6561, 0);      // BOS: speech_emb[start] + speech_pos[0], t3.py:550-551
                 if (p == T - 1) hm.sel_rows[2 * sr.n_sel + sI] = sr.M - 1;
+                if (p == T - 1 && sI == 0 && r.sp.alignment) tap_row(gi, 0, T - 1 - T3_COND_ROWS);      // the BOS row draws token 0
             }
         r.n_prefilled = p1; sr.n_prefill_rows += 2 * chunk; sr.max_prefill_ctx = std::max(sr.max_prefill_ctx, p1);
         if (p1 == T) {
@@ -755,7 +818,7 @@ static int launch_steps(T3Engine* e, T3Engine::Step* steps, int n) {
             for (int r = 0; r < sr.M; ++r) { const int* rec = g.hm[buf].rows + (size_t)r * e->row_stride; e->dbg_emb_rec[2 * r] = rec[0]; e->dbg_emb_rec[2 * r + 1] = rec[1]; }
         }
         if (graphs_ok) {
-            const auto key = std::make_tuple(sr.M, sr.n_sel, e->zero_copy ? buf : 0, n);      // zero-copy: the pinned buffers of `buf` ... are kernel arguments
+            const auto key = std::make_tuple(sr.M, sr.n_sel, e->zero_copy ? buf : 0, n, sr.tapped);      // zero-copy: the pinned buffers of `buf` ... are kernel arguments
             auto it = g.graphs.find(key);
             if (it == g.graphs.end()) {
                 hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
@@ -874,6 +937,20 @@ static int complete_step(T3Engine* e, T3Engine::Step& st, T3StepResult* res, dou
                         r.d_out = e->out_pool.back(); e->out_pool.pop_back();
                         const hipError_t ce = hipMemcpyAsync(r.d_out, e->d_hist + (size_t)r.slot * e->cfg.max_model_len, r.out.size() * 4, hipMemcpyDeviceToDevice, e->groups[gi].stream);
                         if (ce != hipSuccess && !dev_rc) dev_rc = e->fail(T3_E_DEVICE, std::string("hand-off copy of a finished utterance's ids failed: ") + hipGetErrorString(ce));
+                    }
+                }
+                if (r.sp.alignment) {
+                    // the same pattern for its alignment frames: rows 0 .. n_tokens - 1 of the slot's buffer, whole rows of align_ld floats.  Rows that
+                    // steps already enqueued behind this one write (a stop token inside a burst) lie beyond n_tokens and are not part of it.
+                    const size_t bytes = r.out.size() * (size_t)e->align_ld * 4, cap = (size_t)e->cfg.max_model_len * e->align_ld * 4;
+                    hipError_t ce = hipSuccess;
+                    if (!e->align_pool.empty()) { r.d_align = e->align_pool.back(); e->align_pool.pop_back(); }
+                    else ce = hipMalloc((void**)&r.d_align, cap);      // more finished-and-unreleased tapped requests than ever before: the pool grows
+                    if (ce != hipSuccess) { r.d_align = nullptr; if (!dev_rc) dev_rc = e->fail(T3_E_NOMEM, "hipMalloc of " + std::to_string(cap) + " bytes for a finished request's alignment matrix failed"); }
+                    else {
+                        r.align_ld = e->align_ld;
+                        ce = hipMemcpyAsync(r.d_align, e->d_align + (size_t)r.slot * e->cfg.max_model_len * e->align_ld, bytes, hipMemcpyDeviceToDevice, e->groups[gi].stream);
+                        if (ce != hipSuccess && !dev_rc) dev_rc = e->fail(T3_E_DEVICE, std::string("copy of a finished request's alignment matrix failed: ") + hipGetErrorString(ce));
                     }
                 }
                 if (res->n_finished < 64) res->finished_ids[res->n_finished] = r.id;
@@ -1003,6 +1080,7 @@ extern "C" int t3_release_request(T3Handle e, int64_t req_id) {
     if (it == e->reqs.end()) return e->fail(T3_E_NOTFOUND, "unknown request id");
     if (it->second.state != FINISHED) return e->fail(T3_E_STATE, "request still running");
     if (it->second.d_out) e->out_pool.push_back(it->second.d_out);
+    release_align(e, it->second);
     e->reqs.erase(it);
     return T3_OK;
 }
@@ -1045,6 +1123,66 @@ extern "C" int t3_reserve_handoff(T3Handle e, int32_t n_requests) {
     return missing > 0 ? grow_out_pool(e, missing) : T3_OK;
 }
 
+// ---- alignment export ------------------------------------------------------------------------------
+extern "C" int t3_reserve_alignment(T3Handle e, int32_t max_text_tokens) {
+    if (!e || max_text_tokens < 0 || max_text_tokens > 2050) return e ? e->fail(T3_E_INVALID, "max_text_tokens out of range [0, 2050]") : T3_E_INVALID;
+    if (!e->running.empty() || !e->waiting.empty()) return e->fail(T3_E_STATE, "t3_reserve_alignment while requests are queued or running");
+    (void)hipSetDevice(e->cfg.device_id);
+    int rc;
+    if ((rc = drop_graphs(e))) return rc;
+    free_dev(e->d_align); e->d_align = nullptr; e->align_max_text = 0; e->align_ld = 0;
+    for (float* b : e->align_pool) free_dev(b);
+    e->align_pool.clear();
+    if (max_text_tokens == 0) return T3_OK;
+    const int ld = (max_text_tokens + 3) & ~3;
+    const size_t bytes = (size_t)e->cfg.max_seqs * e->cfg.max_model_len * ld * 4;
+    if (hipMalloc((void**)&e->d_align, bytes) != hipSuccess) {
+        e->d_align = nullptr;
+        return e->fail(T3_E_NOMEM, "hipMalloc of " + std::to_string(bytes) + " bytes for the alignment frames (max_seqs x max_model_len x max_text_tokens fp32) failed");
+    }
+    e->align_max_text = max_text_tokens; e->align_ld = ld;
+    return T3_OK;
+}
+
+extern "C" int t3_set_alignment_heads(T3Handle e, const int32_t* layer_head_pairs, int32_t n) {
+    if (!e || !layer_head_pairs) return T3_E_INVALID;
+    if (n < 1 || n > 4) return e->fail(T3_E_INVALID, "between 1 and 4 alignment heads");
+    for (int i = 0; i < n; ++i) {
+        const int L = layer_head_pairs[2 * i], h = layer_head_pairs[2 * i + 1];
+        if (L < 0 || L >= e->cfg.n_layers || h < 0 || h >= H) return e->fail(T3_E_INVALID, "alignment head (layer, head) out of range");
+        if (i > 0 && L <= layer_head_pairs[2 * i - 2]) return e->fail(T3_E_INVALID, "alignment heads need strictly ascending layers");
+    }
+    if (!e->running.empty() || !e->waiting.empty()) return e->fail(T3_E_STATE, "t3_set_alignment_heads while requests are queued or running");
+    (void)hipSetDevice(e->cfg.device_id);
+    int rc;
+    if ((rc = drop_graphs(e))) return rc;
+    for (int i = 0; i < n; ++i) { e->taps[i][0] = layer_head_pairs[2 * i]; e->taps[i][1] = layer_head_pairs[2 * i + 1]; }
+    e->n_taps = n;
+    return T3_OK;
+}
+
+extern "C" int t3_get_alignment(T3Handle e, int64_t req_id, float* out, int32_t* n_frames, int32_t* n_text) {
+    if (!e || !n_frames || !n_text) return T3_E_INVALID;
+    auto it = e->reqs.find(req_id);
+    if (it == e->reqs.end()) return e->fail(T3_E_NOTFOUND, "unknown request id");
+    const Request& r = it->second;
+    if (!r.sp.alignment) return e->fail(T3_E_INVALID, "request " + std::to_string(req_id) + " was not submitted with alignment = 1");
+    if (r.state != FINISHED) return e->fail(T3_E_STATE, "request " + std::to_string(req_id) + " has not finished");
+    const int nf = (int)r.out.size(), nt = (int)r.prompt.size() - 1 - T3_COND_ROWS;
+    const int64_t cap = (int64_t)*n_frames * *n_text;
+    *n_frames = nf; *n_text = nt;
+    if (!out) return T3_OK;
+    if (cap < (int64_t)nf * nt) return e->fail(T3_E_INVALID, "alignment buffer too small: " + std::to_string((int64_t)nf * nt) + " floats needed");
+    if (nf == 0 || nt == 0) return T3_OK;
+    if (!r.d_align) return e->fail(T3_E_DEVICE, "the alignment matrix of request " + std::to_string(req_id) + " could not be kept");
+    (void)hipSetDevice(e->cfg.device_id);
+    for (auto& g : e->groups) if (g.stream) HIP_TRY(hipStreamSynchronize(g.stream));      // the copy-out was queued on a group stream
+    std::vector<float> rows((size_t)nf * r.align_ld);
+    HIP_TRY(hipMemcpy(rows.data(), r.d_align, rows.size() * 4, hipMemcpyDeviceToHost));
+    for (int k = 0; k < nf; ++k) memcpy(out + (size_t)k * nt, rows.data() + (size_t)k * r.align_ld, (size_t)nt * 4);
+    return T3_OK;
+}
+
 extern "C" int t3_pop_finished(T3Handle e, int64_t* ids, int32_t cap) {
     if (!e || (!ids && cap > 0) || cap < 0) return T3_E_INVALID;
     int n = 0;
@@ -1079,6 +1217,7 @@ extern "C" int t3_abort_request(T3Handle e, int64_t req_id) {
         release_slot(e, r);
     }
     if (r.d_out) e->out_pool.push_back(r.d_out);
+    release_align(e, r);
     e->reqs.erase(it);
     return T3_OK;
 }

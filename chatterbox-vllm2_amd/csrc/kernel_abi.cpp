@@ -197,6 +197,52 @@ extern "C" int t3k_rope_attention_fp8(const void* qkv, const int32_t* row_stream
     return rope_attention_impl(qkv, row_stream, row_pos, rows, n_streams, max_pos, out, true, kv_out);
 }
 
+/* The alignment tap (t3_alignment.hip): every row goes into a scrambled paged pool through the prefill path (rope_kv), then ONE tap launch serves every
+ * row (workgroup = row, frame = row) over the span [lo, hi) of its context. */
+extern "C" int t3k_attention_probs(const void* qkv, const int32_t* row_stream, const int32_t* row_pos, int32_t rows, int32_t n_streams, int32_t max_pos,
+                                   int32_t head, int32_t lo, int32_t hi, int32_t kv_dtype, float* out, void* q_rot, void* kv_out) {
+    if (!qkv || !row_stream || !row_pos || !out || rows <= 0 || n_streams <= 0 || max_pos <= 0 || head < 0 || head >= H || lo < 0 || hi <= lo || hi > max_pos ||
+        (kv_dtype != 0 && kv_dtype != 1) || max_pos > 8192 /* the engine's own limit; the tap's LDS strip grows with it */) return T3_E_INVALID;
+    if (!have_device()) return T3_E_DEVICE;
+    for (int r = 0; r < rows; ++r)
+        if (row_stream[r] < 0 || row_stream[r] >= n_streams || row_pos[r] < 0 || row_pos[r] >= max_pos) return T3_E_INVALID;
+    const bool fp8 = kv_dtype == 1;
+    const int max_blocks = (max_pos + KV_BLOCK - 1) / KV_BLOCK, nb = n_streams * max_blocks, span = hi - lo;
+    std::vector<int> table(nb);
+    for (int i = 0; i < nb; ++i) table[i] = (int)(((long)i * 7919 + 13) % nb);
+    {
+        std::vector<char> seen(nb, 0); bool ok = true;
+        for (int i = 0; i < nb; ++i) { if (seen[table[i]]) ok = false; seen[table[i]] = 1; }
+        if (!ok) for (int i = 0; i < nb; ++i) table[i] = nb - 1 - i;
+    }
+    std::vector<float> c((size_t)max_pos * 32), s((size_t)max_pos * 32);
+    rope_tables(max_pos, c.data(), s.data());
+    const int stride = row_stride_words(max_blocks);
+    std::vector<int> recs((size_t)rows * stride, 0);
+    for (int r = 0; r < rows; ++r) {
+        int* rec = recs.data() + (size_t)r * stride;
+        rec[0] = row_stream[r]; rec[1] = row_pos[r]; rec[ROW_ALIGN_FRAME] = r; rec[ROW_ALIGN_NTEXT] = span;
+        for (int b = 0; b < max_blocks; ++b) rec[ROW_HDR + b] = table[(size_t)row_stream[r] * max_blocks + b];
+    }
+    DevBuf dqkv, drec, dc, ds, dq, dkv, dout, dqr, dkvo;
+    K_TRY(dqkv.from(qkv, (size_t)rows * QKV * 2)); K_TRY(drec.from(recs.data(), recs.size() * 4));
+    K_TRY(dc.from(c.data(), c.size() * 4)); K_TRY(ds.from(s.data(), s.size() * 4));
+    K_TRY(dq.alloc((size_t)rows * D * 2)); K_TRY(dkv.alloc((size_t)nb * KV_BLOCK_ELEMS * (fp8 ? 1 : 2), true));
+    K_TRY(dout.alloc((size_t)rows * span * 4, true)); K_TRY(dqr.alloc((size_t)rows * HD * 2, true));
+    RopeArgs ra{dqkv.as<uint16_t>(), dq.as<uint16_t>(), dkv.as<uint16_t>(), drec.as<int>(), stride, dc.as<float>(), ds.as<float>(), rows};
+    K_TRY(fp8 ? launch_rope_kv_fp8(ra, nullptr) : launch_rope_kv(ra, nullptr));
+    // frames_per_slot = 0: the destination row is the frame word alone, i.e. the row index
+    AlignArgs aa{dqkv.as<uint16_t>(), dkv.p, drec.as<int>(), stride, nullptr, dc.as<float>(), ds.as<float>(), dout.as<float>(), rows, head, lo, (max_pos + CHUNK - 1) / CHUNK,
+                 0, span, 0, 1, 1.0f, dqr.as<uint16_t>()};
+    K_TRY(launch_alignment(aa, fp8, nullptr));
+    if (kv_out) { K_TRY(dkvo.alloc((size_t)rows * 2 * D * 2, true)); K_TRY((fp8 ? launch_kv_gather_fp8 : launch_kv_gather)(dkv.as<uint16_t>(), drec.as<int>(), stride, rows, dkvo.as<uint16_t>(), nullptr)); }
+    K_TRY(hipDeviceSynchronize());
+    K_TRY(hipMemcpy(out, dout.p, (size_t)rows * span * 4, hipMemcpyDeviceToHost));
+    if (q_rot) K_TRY(hipMemcpy(q_rot, dqr.p, (size_t)rows * HD * 2, hipMemcpyDeviceToHost));
+    if (kv_out) K_TRY(hipMemcpy(kv_out, dkvo.p, (size_t)rows * 2 * D * 2, hipMemcpyDeviceToHost));
+    return T3_OK;
+}
+
 /* The FUSED decode attention exactly as a decode step launches it (attention_kernel<waves, nt, FUSE = true>: RoPE of q / k, paged
  * write of the newest K / V, attention over the paged context), `steps` consecutive launches of `rows` rows:
  *   - stream r (= row r) holds ctx[r] - 1 context tokens whose pre-RoPE qkv rows are ctx_qkv[content r % n_content][0 .. ctx[r] - 2]

@@ -22,16 +22,12 @@ namespace t3 {
 //     in MEMORY the lane's 16-byte piece sits at piece index 4 t + kg of the fragment (token-major: k_piece() below)
 //   V fragment (dt, ts), lane d + 16 kg, element j  =  V[token 32 ts + 8 kg + j of the chunk][dim 16 dt + d]    (MFMA A operand: rows = dims)
 // so the attention kernel feeds v_mfma_f32_16x16x32_bf16 straight from fully coalesced 1 KiB wave loads.
-__device__ __forceinline__ size_t kv_head_base(int blk, int kv, int h) {
-    return (size_t)blk * KV_BLOCK_ELEMS + (size_t)(kv * H + h) * KV_HEAD_ELEMS;
-}
 // Where the 16-byte piece of lane (token t, dim slice kg) sits inside a K fragment's 1 KiB: token-major (4 t + kg), so that a token's four
 // slices are 64 contiguous bytes and the newest token's K write touches 2 lines per (row, head).  In lane order (t + 16 kg: the MFMA A
 // operand's own order, rounds 1-3; tools/diag/t3_attention_diag.hip -DT3_K_TOKEN_MAJOR=0) they are 256 bytes apart, 8 lines per (row, head), and the write's cost follows the
 // lines touched: C3 21.12 -> 21.27 k tok/s (profiles/r03_k_token_major_*.json).  A wave still loads the same 1 KiB per fragment, each lane
 // from its permuted place.  Every K reader and writer goes through k_piece() / k_lane_piece().
-__device__ __forceinline__ int k_piece(int t, int kg) { return 4 * t + kg; }
-__device__ __forceinline__ int k_lane_piece(int lane) { return 4 * (lane & 15) + (lane >> 4); }      // the piece lane (t = lane % 16, kg = lane / 16) loads
+// (kv_head_base(), k_piece() and k_lane_piece() live in t3_attention_common.h: the alignment tap, t3_alignment.hip, reads the same layout)
 __device__ __forceinline__ size_t k_slot(int tok_in_block, int ds, int kg) {      // start of the 8-element (16 B) piece
     const int ci = tok_in_block / CHUNK, tc = tok_in_block % CHUNK;
     return (size_t)ci * (CHUNK * HD) + (size_t)((tc >> 4) * 2 + ds) * 512 + (size_t)k_piece(tc & 15, kg) * 8;

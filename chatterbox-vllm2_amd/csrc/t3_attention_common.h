@@ -1,10 +1,34 @@
-// Device helpers the two attention translation units share (t3_attention.hip: bf16 pool, t3_attention_fp8.hip: FP8 E4M3 pool): the RoPE of
-// one lane's eight rotation pairs and the wave reductions in the contract's order (DESIGN.md "Attention", "RoPE").  One copy, so both
-// storage formats run the same products, roundings and pairings.
+// Device helpers the attention translation units share (t3_attention.hip: bf16 pool, t3_attention_fp8.hip: FP8 E4M3 pool, t3_alignment.hip:
+// the K-only probability tap over either): where a head's K / V live in the paged pool, the FP8 dequantisation, the RoPE of one lane's eight
+// rotation pairs and the wave reductions in the contract's order (DESIGN.md "Attention", "RoPE").  One copy, so every reader runs the same
+// addresses, products, roundings and pairings.
 #pragma once
+#include "t3_kernels.h"
 #include "t3_device.h"
 
 namespace t3 {
+// ---- paged pool addressing (layouts: t3_attention.hip for bf16, t3_attention_fp8.hip for FP8)
+__device__ __forceinline__ size_t kv_head_base(int blk, int kv, int h) {
+    return (size_t)blk * KV_BLOCK_ELEMS + (size_t)(kv * H + h) * KV_HEAD_ELEMS;
+}
+__device__ __forceinline__ int k_piece(int t, int kg) { return 4 * t + kg; }
+__device__ __forceinline__ int k_lane_piece(int lane) { return 4 * (lane & 15) + (lane >> 4); }      // the piece lane (t = lane % 16, kg = lane / 16) loads
+constexpr int CHUNK8 = CHUNK * HD;      // FP8 pool: bytes of K (or V) of one chunk of one head
+__device__ __forceinline__ size_t kv8_head_base(int blk, int kv, int h) {
+    return (size_t)blk * KV_BLOCK_ELEMS + (size_t)(kv * H + h) * KV_HEAD_ELEMS;
+}
+__device__ __forceinline__ int k8_lane_piece(int lane) { return 4 * (lane & 15) + (lane >> 4); }
+// ---- FP8 (E4M3FN) -> bf16, exact
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+template <bool HI>
+__device__ __forceinline__ uint32_t dq8_pair(uint32_t w) {                           // two e4m3 of the low / high half of w -> packed bf16 pair (exact)
+    union { bf16x2 v; uint32_t u; } c;
+    c.v = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, HI);
+    return c.u;
+}
+__device__ __forceinline__ uint4 dq8_frag(uint32_t w0, uint32_t w1) {                // eight e4m3 bytes -> one MFMA operand fragment of eight bf16
+    return make_uint4(dq8_pair<false>(w0), dq8_pair<true>(w0), dq8_pair<false>(w1), dq8_pair<true>(w1));
+}
 // RoPE (rotate-half, llama3-scaled table): pairs i in [8*part, 8*part+8):  o1 = x1*c - x2*s, o2 = x2*c + x1*s
 // (cos/sin are bf16-valued so both products are exact; one fp32 rounding, then bf16).
 __device__ __forceinline__ void rope8(const uint4& x1, const uint4& x2, const float* c, const float* s, uint4& o1, uint4& o2) {

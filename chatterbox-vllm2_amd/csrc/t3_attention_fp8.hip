@@ -18,7 +18,6 @@ namespace t3 {
 // ------------------------------------------------------------------------------------------------
 // q8 / dequantise.  The clamp runs in VALU in front of the convert, so saturation does not depend on a mode-register bit; NaN stays NaN.
 // ------------------------------------------------------------------------------------------------
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float clamp8(float x) { const float c = fminf(fmaxf(x, -448.0f), 448.0f); return x != x ? x : c; }
 __device__ __forceinline__ uint32_t q8_x4(float a, float b, float c, float d) {      // four fp32 -> four e4m3 bytes, a in the lowest
     const int w = __builtin_amdgcn_cvt_pk_fp8_f32(clamp8(a), clamp8(b), 0, false);
@@ -29,15 +28,7 @@ __device__ __forceinline__ uint2 q8_bf8(const uint4& v) {                       
     return make_uint2(q8_x4(f[0], f[1], f[2], f[3]), q8_x4(f[4], f[5], f[6], f[7]));
 }
 __device__ __forceinline__ uint32_t q8_one(uint32_t bf) { return q8_x4(bf2f((uint16_t)bf), 0.0f, 0.0f, 0.0f) & 0xffu; }
-template <bool HI>
-__device__ __forceinline__ uint32_t dq8_pair(uint32_t w) {                           // two e4m3 of the low / high half of w -> packed bf16 pair (exact)
-    union { bf16x2 v; uint32_t u; } c;
-    c.v = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, HI);
-    return c.u;
-}
-__device__ __forceinline__ uint4 dq8_frag(uint32_t w0, uint32_t w1) {                // eight e4m3 bytes -> one MFMA operand fragment of eight bf16
-    return make_uint4(dq8_pair<false>(w0), dq8_pair<true>(w0), dq8_pair<false>(w1), dq8_pair<true>(w1));
-}
+// (dq8_pair() / dq8_frag(), the dequantisation in front of every MFMA: t3_attention_common.h, shared with t3_alignment.hip)
 __device__ __forceinline__ uint32_t dq8_one(uint32_t byte) { return dq8_pair<false>(byte) & 0xffffu; }
 
 __global__ __launch_bounds__(256) void fp8_roundtrip_kernel(const float* x, float* y, int n) {      // parity hook: y = dequantised q8(x), four values per lane
@@ -67,11 +58,7 @@ hipError_t launch_fp8_roundtrip(const float* x, float* y, int n, hipStream_t s) 
 // The head regions keep KV_HEAD_PAD = 512 elements (here 512 bytes) between them: 16.5 KiB per head instead of a power of two, and a block of
 // exactly half the bf16 block's bytes.  The value is carried over from the bf16 pool, not measured for one-byte elements.
 // ------------------------------------------------------------------------------------------------
-constexpr int CHUNK8 = CHUNK * HD;      // bytes of K (or V) of one chunk of one head
-__device__ __forceinline__ size_t kv8_head_base(int blk, int kv, int h) {
-    return (size_t)blk * KV_BLOCK_ELEMS + (size_t)(kv * H + h) * KV_HEAD_ELEMS;
-}
-__device__ __forceinline__ int k8_lane_piece(int lane) { return 4 * (lane & 15) + (lane >> 4); }
+// (CHUNK8, kv8_head_base() and k8_lane_piece(): t3_attention_common.h)
 __device__ __forceinline__ size_t k8_off(int tok_in_block, int kg) { return (size_t)tok_in_block * HD + kg * 16; }      // 16 tt-major tokens x 64 B = the piece order above
 __device__ __forceinline__ size_t v8_off(int tok_in_block, int dim) {                                                     // one byte
     const int ci = tok_in_block / CHUNK, tc = tok_in_block % CHUNK;

@@ -69,9 +69,12 @@ void set_pgemm_min_rows(int rows);   // row count from which launch_gemm takes t
 void set_pgemm_wide_rows(int rows);  // row count from which its 4-segment forms take 128 x 128 tiles (0 = never; < 0 = default 2048)
 
 // Per-row record of a step (int32 words), built by the scheduler and uploaded once per step:
-//   [0] stream  [1] position  [2] embed kind  [3] embed a  [4] embed b  [5..7] unused  [8 ..] KV block ids of the row's stream
+//   [0] stream  [1] position  [2] embed kind  [3] embed a  [4] embed b  [5] alignment frame  [6] alignment n_text  [7] unused  [8 ..] KV block ids of the row's stream
 // One lookup gives a kernel everything it needs to address the row's paged KV (no stream -> block-table hop).
+// [5], [6]: read by the alignment tap only (t3_alignment.hip).  frame = index of the token this row's logits produce, -1 = the row is not
+// tapped; n_text = text ids of its prompt.
 constexpr int ROW_HDR = 8;
+constexpr int ROW_ALIGN_FRAME = 5, ROW_ALIGN_NTEXT = 6;
 inline int row_stride_words(int max_blocks) { return ROW_HDR + ((max_blocks + 3) & ~3); }
 
 struct EmbedArgs {
@@ -125,6 +128,25 @@ hipError_t launch_rope_kv_fp8(const RopeArgs& a, hipStream_t s);
 hipError_t launch_attention_fp8(const AttnArgs& a, hipStream_t s);
 hipError_t launch_kv_gather_fp8(const uint16_t* kv_layer, const int* rowrec, int row_stride, int rows, uint16_t* out, hipStream_t s);
 hipError_t launch_fp8_roundtrip(const float* x, float* y, int n, hipStream_t s);   // parity hook: y = dequantised q8(x)
+
+// The alignment tap (t3_alignment.hip): attention probabilities of ONE head over the span [lo, lo + n_text) of each tapped row's context,
+// K only.  Workgroup i serves row sel_rows[2 i] (the conditional row of sampled utterance i; sel_rows null: row i) and leaves at once where
+// the row record's frame word is -1.  Destination: out[((stream / 2) * frames_per_slot + frame) * ld + t].
+struct AlignArgs {
+    const uint16_t* qkv;       // [rows][3072] pre-RoPE: the step's qkv buffer
+    const void* kv_layer;      // the layer's pool (bf16, or one-byte E4M3 elements), holding the rows' newest K already
+    const int* rowrec; int row_stride;
+    const int* sel_rows;       // nullable
+    const float *cos_t, *sin_t;
+    float* out;
+    int n_wg;                  // workgroups: sampled utterances of the step (or rows)
+    int head, lo, max_chunks;
+    int frames_per_slot, ld;
+    int tap, n_taps; float inv_taps;     // tap 0 stores, later taps add, tap n_taps - 1 scales by inv_taps
+    uint16_t* q_rot_out = nullptr;       // nullable (parity hook): [rows][64] the rotated q the tap used
+};
+hipError_t launch_alignment(const AlignArgs& a, bool fp8, hipStream_t s);
+hipError_t launch_alignment_clear(float* p, size_t n, hipStream_t s);   // p[0 .. n) = 0 by a kernel; n a multiple of 4, p 16-byte aligned
 
 struct SampleArgs {
     const uint16_t* logits;    // [2*n][ldl] bf16: row 2i cond, 2i+1 uncond

@@ -36,7 +36,7 @@ class T3Sampling(ct.Structure):
         ("temperature", ct.c_float), ("top_p", ct.c_float), ("min_p", ct.c_float),
         ("repetition_penalty", ct.c_float), ("presence_penalty", ct.c_float), ("frequency_penalty", ct.c_float),
         ("top_k", ct.c_int32), ("max_tokens", ct.c_int32), ("ignore_eos", ct.c_int32), ("stop_token", ct.c_int32),
-        ("seed", ct.c_uint64), ("uid", ct.c_uint64), ("pos_policy", ct.c_int32), ("_pad", ct.c_int32),
+        ("seed", ct.c_uint64), ("uid", ct.c_uint64), ("pos_policy", ct.c_int32), ("alignment", ct.c_int32),
     ]
 
 
@@ -64,6 +64,7 @@ ABI_SYMBOLS = [
     "t3_clean_tokens", "t3_debug_logits", "t3_step_times", "t3_stats", "t3_reset_stats", "t3_set_profile", "t3_set_profile_kernel", "t3_kernel_ms",
     "t3k_gemm", "t3k_norm_gemm", "t3k_qkv_gemm", "t3k_head_gemm", "t3k_gemm_resid", "t3k_silu_mul_gemm", "t3k_rope_attention", "t3k_decode_attention", "t3k_sample", "t3k_sample_support", "t3k_expf",
     "t3k_fp8_roundtrip", "t3k_rope_attention_fp8", "t3k_decode_attention_fp8",
+    "t3_reserve_alignment", "t3_set_alignment_heads", "t3_get_alignment", "t3k_attention_probs",
     "t3_cond_create", "t3_cond_destroy", "t3_cond_last_error", "t3_cond_load_tensor", "t3_cond_encode", "t3_cond_emotion_row",
     "t3k_ce_layernorm", "t3k_ce_linear", "t3k_ce_attention", "t3k_set_prefill_rows", "t3k_set_prefill_wide_rows",
 ]
@@ -133,6 +134,10 @@ def load_library():
     L.t3k_fp8_roundtrip.argtypes = [vp, vp, i32]
     L.t3k_rope_attention_fp8.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     L.t3k_decode_attention_fp8.argtypes = [vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp]
+    L.t3_reserve_alignment.argtypes = [vp, i32]
+    L.t3_set_alignment_heads.argtypes = [vp, vp, i32]
+    L.t3_get_alignment.argtypes = [vp, i64, vp, ct.POINTER(i32), ct.POINTER(i32)]
+    L.t3k_attention_probs.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]
     L.t3_cond_create.argtypes = [i32, ct.POINTER(vp)]
     L.t3_cond_destroy.argtypes = [vp]
     L.t3_cond_last_error.restype = ct.c_char_p; L.t3_cond_last_error.argtypes = [vp]
@@ -166,10 +171,10 @@ def _raise(code: int, msg: str):
 
 def make_sampling(temperature=0.8, top_p=1.0, min_p=0.0, repetition_penalty=2.0, presence_penalty=0.0,
                   frequency_penalty=0.0, top_k=0, max_tokens=1000, ignore_eos=False,
-                  stop_token=C.STOP_SPEECH_TOKEN, seed=0, uid=0, pos_policy=0) -> T3Sampling:
+                  stop_token=C.STOP_SPEECH_TOKEN, seed=0, uid=0, pos_policy=0, alignment=False) -> T3Sampling:
     return T3Sampling(float(temperature), float(top_p), float(min_p), float(repetition_penalty),
                       float(presence_penalty), float(frequency_penalty), int(top_k), int(max_tokens),
-                      int(bool(ignore_eos)), int(stop_token), int(seed), int(uid), int(pos_policy), 0)
+                      int(bool(ignore_eos)), int(stop_token), int(seed), int(uid), int(pos_policy), int(bool(alignment)))
 
 
 # storage formats of the paged KV pool (T3EngineConfig.kv_cache_dtype), under vLLM's names for them
@@ -199,6 +204,7 @@ class T3Engine:
         self.cfg = T3EngineConfig(device_id, n_layers, text_vocab, max_model_len, max_seqs, max_batched_rows,
                                   int(kv_bytes), float(gpu_memory_utilization), float(cfg_scale),
                                   int(enforce_eager), int(debug_logits), int(n_groups), kv_code)
+        self.alignment_max_text = 0       # text ids the alignment frames are reserved for (reserve_alignment)
         self.h = ct.c_void_p()
         rc = self.lib.t3_create(ct.byref(self.cfg), ct.byref(self.h))
         if rc:
@@ -301,6 +307,26 @@ class T3Engine:
         """Keep finished utterances' ids in device memory (n_requests > 0: buffers for that many are made now) or stop doing so (0)."""
         self._chk(self.lib.t3_reserve_handoff(self.h, int(n_requests)))
         self.keeps_device_ids = int(n_requests) > 0
+
+    def reserve_alignment(self, max_text_tokens: int):
+        """Allocate (or, with 0, free) the per-slot alignment frames: max_seqs x max_model_len x max_text_tokens fp32."""
+        self.alignment_max_text = 0       # a reserve that fails leaves no buffer behind
+        self._chk(self.lib.t3_reserve_alignment(self.h, int(max_text_tokens)))
+        self.alignment_max_text = int(max_text_tokens)
+
+    def set_alignment_heads(self, layer_head_pairs: Sequence[Tuple[int, int]]):
+        """The (layer, head) taps the alignment matrix averages (1..4, layers strictly ascending); default: the reference's three heads."""
+        a = np.ascontiguousarray(np.asarray(layer_head_pairs, dtype=np.int32).reshape(-1, 2))
+        self._chk(self.lib.t3_set_alignment_heads(self.h, ct.c_void_p(a.ctypes.data), len(a)))
+
+    def get_alignment(self, req_id: int) -> torch.Tensor:
+        """The alignment matrix [n_tokens, n_text] (CPU float32) of a finished, unreleased request submitted with alignment=True:
+        row k = what the tapped heads pay to the text positions while token k is drawn (upstream's per-frame A_chunk)."""
+        nf = ct.c_int32(0); nt = ct.c_int32(0)
+        self._chk(self.lib.t3_get_alignment(self.h, int(req_id), None, ct.byref(nf), ct.byref(nt)))
+        out = torch.zeros(int(nf.value), int(nt.value), dtype=torch.float32)
+        self._chk(self.lib.t3_get_alignment(self.h, int(req_id), ct.c_void_p(out.data_ptr()), ct.byref(nf), ct.byref(nt)))
+        return out
 
     def pop_finished(self, cap: int = 4096) -> List[int]:
         """ids of the requests that finished since the last call, oldest first"""
@@ -445,6 +471,18 @@ def k_decode_attention(ctx_qkv: torch.Tensor, new_qkv: torch.Tensor, ctx, max_po
     _chk_k(load_library().t3k_decode_attention(ctx_qkv.data_ptr(), ctx_qkv.shape[0], ctx_qkv.shape[1], new_qkv.data_ptr(), cx.ctypes.data,
                                                rows, steps, int(max_pos), int(waves), out.data_ptr(), kvn.data_ptr()), "t3k_decode_attention")
     return out, kvn
+
+
+def k_attention_probs(qkv: torch.Tensor, row_stream, row_pos, n_streams: int, max_pos: int, head: int, lo: int, hi: int, kv_dtype: str = "bf16"):
+    """The alignment tap kernel: rows written through the prefill path, then softmax(q_rot . K_stored / 8) of `head` over every row's context,
+    span [lo, hi) -> (probs [rows, hi - lo] fp32, 0 beyond the row's context; q_rot [rows, 64] bf16; stored K / V [rows, 2, 1024] bf16)."""
+    qkv = _bf(qkv)
+    rs = np.ascontiguousarray(np.asarray(row_stream, dtype=np.int32)); rp = np.ascontiguousarray(np.asarray(row_pos, dtype=np.int32))
+    rows = qkv.shape[0]
+    out = torch.empty(rows, hi - lo, dtype=torch.float32); q = torch.empty(rows, 64, dtype=torch.bfloat16); kv = torch.empty(rows, 2, C.HIDDEN, dtype=torch.bfloat16)
+    _chk_k(load_library().t3k_attention_probs(qkv.data_ptr(), rs.ctypes.data, rp.ctypes.data, rows, n_streams, max_pos, int(head), int(lo), int(hi),
+                                              kv_cache_dtype_code(kv_dtype), out.data_ptr(), q.data_ptr(), kv.data_ptr()), "t3k_attention_probs")
+    return out, q, kv
 
 
 def k_fp8_roundtrip(x: torch.Tensor) -> torch.Tensor:

@@ -36,7 +36,7 @@ class SamplingParams:
     def __init__(self, n: int = 1, temperature: float = 1.0, top_p: float = 1.0, top_k: int = 0, min_p: float = 0.0,
                  repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
                  seed: Optional[int] = None, stop_token_ids: Optional[List[int]] = None, max_tokens: Optional[int] = 16,
-                 ignore_eos: bool = False, pos_policy: int = 0, **kwargs):
+                 ignore_eos: bool = False, pos_policy: int = 0, alignment: bool = False, **kwargs):
         for k, v in kwargs.items():
             if k not in self._IGNORED:
                 raise TypeError(f"SamplingParams got an unexpected keyword argument {k!r}")
@@ -60,6 +60,9 @@ class SamplingParams:
         self.repetition_penalty, self.presence_penalty, self.frequency_penalty = repetition_penalty, presence_penalty, frequency_penalty
         self.seed, self.stop_token_ids, self.max_tokens, self.ignore_eos = seed, list(stop_token_ids or []), max_tokens, ignore_eos
         self.pos_policy = pos_policy
+        # extension: keep the text-speech alignment matrix of the request (CompletionOutput.alignment) -- what upstream's
+        # AlignmentStreamAnalyzer reads from its attention hooks and a vLLM engine cannot hand out
+        self.alignment = bool(alignment)
 
     def __repr__(self):
         return ("SamplingParams(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in (
@@ -75,6 +78,7 @@ class CompletionOutput:
     logprobs: Optional[Any] = None
     finish_reason: Optional[str] = None
     stop_reason: Union[int, str, None] = None
+    alignment: Optional[torch.Tensor] = None      # SamplingParams(alignment=True): CPU float32 [n_tokens, n_text], row k = frame k's attention over the text
 
 
 @dataclass
@@ -97,7 +101,7 @@ class LLM:
                  max_num_batched_tokens: int = 0, seed: int = 0, load_format: str = "auto", dtype: str = "bfloat16",
                  device_id: Optional[int] = None, tokenizer_file: Optional[str] = None, num_hidden_layers: Optional[int] = None,
                  kv_cache_bytes: int = 0, debug_logits: bool = False, honor_enforce_eager: Optional[bool] = None,
-                 kv_cache_dtype: Optional[str] = None, **kwargs):
+                 kv_cache_dtype: Optional[str] = None, alignment_max_text: int = 0, **kwargs):
         if task != "generate":
             raise ValueError("only task='generate' exists on the T3 path")
         if dtype not in ("bfloat16", "auto", torch.bfloat16):
@@ -138,6 +142,10 @@ class LLM:
         else:
             self.engine.load_tensors(iter_safetensors(ckpt))
         self.engine.finalize()
+        # alignment export: frame buffers for texts of up to alignment_max_text ids are made now; 0 = the first generate() with a tapped
+        # request reserves for the longest text of that call
+        if alignment_max_text > 0:
+            self.engine.reserve_alignment(alignment_max_text)
         tf = find_tokenizer_file(self.tokenizer_kind, model if model and os.path.isdir(model) else None, tokenizer_file)
         self.tokenizer = TextTokenizer(self.tokenizer_kind, tf) if tf else None
         self._next_id = 0
@@ -215,14 +223,15 @@ class LLM:
             if keep_for_handoff and not kept_before:
                 self.engine.reserve_handoff(0)      # finished requests keep the buffers they hold; no new ones are made
         outs = []
-        for rid, text, final in metas:
+        for rid, text, final, tap in metas:
             toks, fr = self.engine.get_output(rid)
+            align = self.engine.get_alignment(rid) if tap else None
             if not keep_for_handoff:
                 self.engine.release(rid)
             reason = {1: "stop", 2: "length"}.get(fr)
             outs.append(RequestOutput(request_id=str(rid), prompt=text, prompt_token_ids=final,
                                       outputs=[CompletionOutput(index=0, text="", token_ids=toks, finish_reason=reason,
-                                                                stop_reason=(toks[-1] if fr == 1 else None))]))
+                                                                stop_reason=(toks[-1] if fr == 1 else None), alignment=align)]))
         return outs
 
     def handoff_tokens(self, outputs: Sequence[RequestOutput], text_token_counts: Sequence[int], range_filter: bool = True):
@@ -241,8 +250,11 @@ class LLM:
                     pass
 
     def _queue(self, prompts, sps, uids, metas, queued):
-        for i, (p, sp) in enumerate(zip(prompts, sps)):
-            text, tids, cond = self._text_ids(p)
+        texts = [self._text_ids(p) for p in prompts]
+        tapped = [len(t[1]) for t, sp in zip(texts, sps) if sp.alignment]      # text ids per tapped request
+        if tapped and max(tapped) > self.engine.alignment_max_text:
+            self.engine.reserve_alignment(max(tapped))
+        for i, ((text, tids, cond), sp) in enumerate(zip(texts, sps)):
             final = assemble_prompt_ids(tids)
             stop = -1
             if sp.stop_token_ids:
@@ -259,11 +271,11 @@ class LLM:
             esp = make_sampling(temperature=sp.temperature, top_p=sp.top_p, min_p=sp.min_p, repetition_penalty=sp.repetition_penalty,
                                 presence_penalty=sp.presence_penalty, frequency_penalty=sp.frequency_penalty,
                                 top_k=max(0, sp.top_k), max_tokens=max_tokens, ignore_eos=sp.ignore_eos, stop_token=stop,
-                                seed=self.seed if sp.seed is None else sp.seed, uid=uid, pos_policy=sp.pos_policy)
+                                seed=self.seed if sp.seed is None else sp.seed, uid=uid, pos_policy=sp.pos_policy, alignment=sp.alignment)
             rid = self._next_id; self._next_id += 1
             self.engine.add_request(rid, final, cond, esp)
             queued.append(rid)
-            metas.append((rid, text, final))
+            metas.append((rid, text, final, sp.alignment))
 
     def shutdown(self):
         self.engine.close()

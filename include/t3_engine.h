@@ -74,7 +74,9 @@ typedef struct {
                                   composition or on data-parallel sharding */
     int32_t pos_policy;        /* 0: k-th generated token uses speech_pos_emb[k] (SURVEY.md 9 Q1 "exact");
                                   1: index 0 for every decode token (the literal fallback of t3.py:464) */
-    int32_t _pad;
+    int32_t alignment;         /* 1: keep the text-speech alignment matrix of this request (t3_get_alignment; needs t3_reserve_alignment);
+                                  0: off (default).  Any other value is T3_E_INVALID.  Token ids never depend on it.  This was padding: a C
+                                  caller must zero it */
 } T3Sampling;
 
 typedef struct {
@@ -173,6 +175,30 @@ int t3_handoff_tokens(T3Handle h, const int64_t* req_ids, int32_t n, const int32
  * utterances exist BEFORE the step loop runs (max_model_len int32 each).  If more than that finish unreleased, the pool grows inside
  * the loop and an allocation failure there is reported by the step call (T3_E_NOMEM), not by a later t3_handoff_tokens. */
 int t3_reserve_handoff(T3Handle h, int32_t n_requests);
+
+/* ---- text-speech alignment export -------------------------------------------------------------------------------------
+ * What the upstream AlignmentStreamAnalyzer reads from its attention hooks (LLAMA_ALIGNED_HEADS) and the vLLM port lost
+ * (alignment_stream_analyzer.py:139-141 falls back to frame // 2): for a request submitted with T3Sampling.alignment = 1, the fp32 matrix
+ *   A[k][t] = mean over the configured (layer, head) taps of softmax_j(q_k . K_j / 8)[34 + t],   k < n_tokens, t < n_text
+ * where q_k is the rotated query of the CONDITIONAL stream's row whose logits produced token k (position T - 1 + k; k = 0 is the BOS row of
+ * the prefill), j runs over that row's whole causal context, 34 + t over the text span [34, T - 1) of the prompt, and K is the key as the
+ * pool stores it (bf16, or the dequantised E4M3 value).  Row k is upstream's per-frame `A_chunk`.  With alignment = 0 a step launches exactly
+ * what it launches without this feature.
+ * t3_reserve_alignment: allocates (max_text_tokens > 0) or frees (0) the per-slot frame buffers, max_seqs x max_model_len x max_text_tokens
+ * (rounded up to a multiple of 4) fp32; T3_E_NOMEM names the byte count.  Not valid while requests are queued or running.  A request with
+ * alignment = 1 is T3_E_STATE before a reserve and T3_E_INVALID when its text is longer than the reserve.  A reserve and t3_set_alignment_heads
+ * drop the captured decode-step graphs (they carry the buffer, its pitch and the taps); the next steps capture again.  The matrices of finished
+ * requests live in pooled buffers of max_model_len x max_text_tokens fp32 that t3_release_request gives back for reuse. */
+int t3_reserve_alignment(T3Handle h, int32_t max_text_tokens);
+/* The taps: n (1..4) pairs (layer, head), layers strictly ascending and < n_layers, heads < 16.  Default: the reference's three heads in layer
+ * order, (9, 2), (12, 15), (13, 11), restricted to the layers that exist; if none exists and none was set, an alignment = 1 request is
+ * T3_E_STATE.  Valid only while no request is queued or running (T3_E_STATE otherwise). */
+int t3_set_alignment_heads(T3Handle h, const int32_t* layer_head_pairs, int32_t n);
+/* The matrix of a FINISHED, not yet released request, row-major [n_frames][n_text].  On entry *n_frames x *n_text is the capacity of out in
+ * floats (out may be NULL to ask for the extents only); on exit they hold the real extents: n_frames = the number of tokens t3_get_output
+ * returns, n_text = T - 35.  Unknown (or released) id: T3_E_NOTFOUND; a request submitted with alignment = 0 or a buffer too small:
+ * T3_E_INVALID; not finished: T3_E_STATE. */
+int t3_get_alignment(T3Handle h, int64_t req_id, float* out, int32_t* n_frames, int32_t* n_text);
 
 /* ---- parity / measurement hooks --------------------------------------------------------- */
 /* post-CFG logits [8194] (speech-space, before the 2500-wide -inf pad of t3.py:669-672) of the
@@ -279,6 +305,13 @@ int t3k_rope_attention_fp8(const void* qkv_bf16, const int32_t* row_stream, cons
 /* t3k_decode_attention over an FP8 pool: same arguments and meaning, kv_new read back dequantised. */
 int t3k_decode_attention_fp8(const void* ctx_qkv_bf16, int32_t n_content, int32_t content_rows, const void* new_qkv_bf16, const int32_t* ctx,
                              int32_t rows, int32_t steps, int32_t max_pos, int32_t waves, void* out_bf16, void* kv_new_bf16);
+/* The alignment tap kernel (t3_alignment.hip) on host buffers.  Every row is written through the prefill path (RoPE + paged write, as
+ * t3k_rope_attention / t3k_rope_attention_fp8 do; kv_dtype 0 = bf16 pool, 1 = FP8), then the tap runs for EVERY row over the span [lo, hi) of
+ * its stream: out [rows][hi - lo] = softmax over the row's context 0 .. row_pos of head `head`; positions at or beyond the row's own context
+ * length come back as 0.  q_rot (nullable) bf16 [rows][64] = the rotated q the tap used; kv (nullable) bf16 [rows][2][1024] = the stored K / V
+ * of every row's position (dequantised for the FP8 pool). */
+int t3k_attention_probs(const void* qkv_bf16, const int32_t* row_stream, const int32_t* row_pos, int32_t rows, int32_t n_streams, int32_t max_pos,
+                        int32_t head, int32_t lo, int32_t hi, int32_t kv_dtype, float* out_f32, void* q_rot_bf16, void* kv_bf16);
 /* the hand-off kernel on host buffers (one utterance): out [ld] padded with 0, *len = kept tokens */
 int t3k_handoff(const int32_t* speech_ids, int32_t n, int32_t text_token_count, int32_t flags, int32_t* out, int32_t ld, int32_t* len);
 /* Row count from which the GEMM launcher switches to its prefill schedule (same numbers, LDS-tiled); process-wide.
