@@ -60,6 +60,7 @@ struct Request {
     int32_t* d_out = nullptr;         // finished: the utterance's speech-space ids on the device (f4 hand-off), from the engine's buffer pool
     float* d_align = nullptr;         // finished, sp.alignment: its rows of the slot's alignment frames [out.size()][align_ld], a buffer of its own
     int align_ld = 0;                 // ... with the row pitch of the reserve it ran under
+    bool has_guard = false;           // finished, sp.alignment == 2: the slot's guard state words sit in the last GUARD_STATE_WORDS floats of d_align
     double t_add = 0, t_admit = 0, t_first = 0, t_finish = 0;     // seconds since the engine was created (t3_get_timing)
 };
 
@@ -120,12 +121,13 @@ struct T3Engine {
         uint64_t waited_admit_seq = 0;     // the admission this group's stream has been ordered behind
         hipEvent_t ev_done[NBUF] = {};
         int rcap = 0;              // row budget per step
-        std::map<std::tuple<int, int, int, int, bool>, hipGraphExec_t> graphs;   // (M, n_sel, first staging buffer, steps, tapped) -> captured decode step(s)
+        std::map<std::tuple<int, int, int, int, int>, hipGraphExec_t> graphs;   // (M, n_sel, first staging buffer, steps, tapped + 2 guarded) -> captured decode step(s)
     };
     // One enqueued step: what the scheduler put on each group's stream, kept until its tokens are back.
     struct StepRec {
         int M = 0, n_sel = 0, n_prefill_rows = 0, decode_rows = 0;
         bool tapped = false;           // a sampled row of the step feeds the alignment export: the tap launches follow their layers' attention
+        bool guarded = false;          // ... and one of them is guarded: the guard launch follows the last tap, the sampler obeys its control words
         int max_prefill_ctx = 0;       // longest context among the step's prefill rows (sizes the tile attention's LDS)
         double sum_ctx = 0;
         std::vector<Request*> sampled;
@@ -165,6 +167,9 @@ struct T3Engine {
     std::vector<float*> align_pool;    // free per-request matrix buffers of the current reserve (max_model_len x align_ld each): a finished request
                                        // takes one, its release gives it back, so a steady serving loop neither allocates nor frees inside the step loop
     int taps[4][2] = {}; int n_taps = 0;    // (layer, head), layers strictly ascending
+    // alignment guard (t3_set_alignment_guard, t3_guard.hip): per slot GUARD_STATE_WORDS state words and one control word; null = disabled
+    int *d_guard_state = nullptr, *d_guard_ctl = nullptr;
+    T3GuardParams guard{};
     std::deque<int64_t> finished_q;    // ids finished since the last t3_pop_finished (T3StepResult carries only the first 64 of a step)
     uint16_t* d_dbg_emb = nullptr;     // debug_logits: the embedded input rows of the most recent step (t3_debug_embeddings)
     std::vector<int> dbg_emb_rec;      // their (stream, position) pairs
@@ -273,7 +278,7 @@ extern "C" int t3_destroy(T3Handle e) {
     free_dev(e->d_cond); free_dev(e->d_counts); free_dev(e->d_sp); free_dev(e->d_dbg); free_dev(e->d_hist);
     for (void* b : e->out_slabs) free_dev(b);      // every hand-off buffer (pooled or held by a request) lives in one of these
     free_dev(e->d_handoff_items); free_dev(e->d_dbg_emb);
-    free_dev(e->d_align);
+    free_dev(e->d_align); free_dev(e->d_guard_state); free_dev(e->d_guard_ctl);
     for (float* b : e->align_pool) free_dev(b);
     for (auto& kv : e->reqs) free_dev(kv.second.d_align);
     if (e->ev_handoff) (void)hipEventDestroy(e->ev_handoff);
@@ -507,7 +512,12 @@ extern "C" int t3_add_request(T3Handle e, int64_t req_id, const int32_t* ids, in
         uint32_t u; memcpy(&u, cond + i, 4);
         if ((u & 0x7f800000u) == 0x7f800000u) return e->fail(T3_E_INVALID, "conditioning embedding contains a non-finite value");
     }
-    if (sp->alignment != 0 && sp->alignment != 1) return e->fail(T3_E_INVALID, "T3Sampling.alignment must be 0 or 1");
+    if (sp->alignment < 0 || sp->alignment > 2) return e->fail(T3_E_INVALID, "T3Sampling.alignment must be 0, 1 or 2");
+    if (sp->alignment == 2) {
+        if (sp->stop_token < 0 || sp->stop_token >= V) return e->fail(T3_E_INVALID, "a guarded request (alignment = 2) needs a stop_token in [0, 8194)");
+        if (sp->ignore_eos) return e->fail(T3_E_INVALID, "a guarded request (alignment = 2) cannot ignore the stop token it is made to draw");
+        if (!e->d_guard_state) return e->fail(T3_E_STATE, "guarded request (alignment = 2) before t3_set_alignment_guard");
+    }
     if (sp->alignment) {
         if (!e->d_align) return e->fail(T3_E_STATE, "alignment export asked for before t3_reserve_alignment");
         if (e->n_taps == 0) return e->fail(T3_E_STATE, "no alignment head: none of the default taps' layers exists and t3_set_alignment_heads was not called");
@@ -575,6 +585,8 @@ static int admit(T3Engine* e) {
         // stream, not the admission stream: the previous occupant's copy-out (complete_step) was queued there, and the clear must stay behind it.
         if (r.sp.alignment)
             HIP_TRY(launch_alignment_clear(e->d_align + (size_t)slot * e->cfg.max_model_len * e->align_ld, (size_t)r.limit * e->align_ld, e->groups[slot % e->n_groups].stream));
+        // the guard's state and control word of the slot, on the same stream for the same reason (the previous occupant's state is copied out there)
+        if (r.sp.alignment == 2) HIP_TRY(launch_guard_reset(e->d_guard_state, e->d_guard_ctl, slot, e->groups[slot % e->n_groups].stream));
         // r.cond / r.sp are kept alive in the request map until the copy is consumed (stream-ordered, pageable -> staged synchronously)
         e->running.push_back(r.id);
     }
@@ -685,7 +697,14 @@ static int launch_sample_phase(T3Engine* e, T3Engine::Group& g, const T3Engine::
     // loads in front of the activation loads)
     const int* sel_rows = (sr.n_prefill_rows == 0 && sr.M == 2 * n_sel) ? nullptr : g.dm.sel_rows;
     { Prof p(e, K_HEAD, s); GemmArgs a{g.h, (const uint4*)e->head, 2 * n_sel, D, V, g.logits, VPAD, 4, 1, sel_rows, HEAD_TILES}; HIP_TRY(launch_gemm(a, EPI_BF16, choose_mt(2 * n_sel, VPAD / 16, 4, true), s)); }
-    { Prof p(e, K_SAMPLE, s); SampleArgs sa{g.logits, VPAD, g.dm.sel, e->d_counts, e->d_sp, e->cfg.cfg_scale, g.dm.out_tok, e->d_dbg, n_sel, e->d_hist, e->cfg.max_model_len, e->zero_copy ? g.h_out_tok[buf] : nullptr}; HIP_TRY(launch_sampler(sa, s)); }
+    if (sr.guarded) {      // every tap of the step has run (the layers are behind us): the guard reads the completed frames and leaves the sampler's control words
+        GuardArgs ga{e->d_align, e->cfg.max_model_len, e->align_ld, g.dm.rows, e->row_stride, g.dm.sel_rows, g.dm.sel, e->d_sp, e->d_hist, e->cfg.max_model_len,
+                     e->d_guard_state, e->d_guard_ctl, n_sel, e->guard};
+        HIP_TRY(launch_guard(ga, s));
+    }
+    { Prof p(e, K_SAMPLE, s); SampleArgs sa{g.logits, VPAD, g.dm.sel, e->d_counts, e->d_sp, e->cfg.cfg_scale, g.dm.out_tok, e->d_dbg, n_sel, e->d_hist, e->cfg.max_model_len, e->zero_copy ? g.h_out_tok[buf] : nullptr};
+      if (sr.guarded) sa.eos_ctl = e->d_guard_ctl;
+      HIP_TRY(launch_sampler(sa, s)); }
     return T3_OK;
 }
 static int launch_step(T3Engine* e, T3Engine::Group& g, const T3Engine::StepRec& sr, int buf, hipStream_t s) {
@@ -716,10 +735,10 @@ static int build_step(T3Engine* e, T3Engine::Step& st, bool may_admit) {
         memcpy(rec + ROW_HDR, &e->h_block_table[(size_t)stream * e->max_blocks], (size_t)e->max_blocks * 4);
         ++sr.M;
     };
-    auto tap_row = [&](int gi, int frame, int n_text) {      // the row just added is a tapped request's conditional sampled row
+    auto tap_row = [&](int gi, int frame, int n_text, bool guarded) {      // the row just added is a tapped request's conditional sampled row
         T3Engine::StepRec& sr = st.g[gi];
         int* rec = e->groups[gi].hm[buf].rows + (size_t)(sr.M - 1) * e->row_stride;
-        rec[ROW_ALIGN_FRAME] = frame; rec[ROW_ALIGN_NTEXT] = n_text; sr.tapped = true;
+        rec[ROW_ALIGN_FRAME] = frame; rec[ROW_ALIGN_NTEXT] = n_text; sr.tapped = true; sr.guarded |= guarded;
     };
     // decode rows of every running utterance, then prefill rows within the group's budget.  Longest context first: the fused attention's
     // workgroups (one per row and head, dispatched in row order) take a time proportional to the row's context, and a long row handed out
@@ -744,7 +763,7 @@ static int build_step(T3Engine* e, T3Engine::Step& st, bool may_admit) {
         const bool known = (int)r.out.size() == n;
         const int kind = known ? EMB_SPEECH : EMB_SPEECH_PREV, a = known ? r.out.back() : r.last_idx;
         hm.sel_rows[2 * sr.n_sel] = sr.M;     add_row(gi, 2 * r.slot, pos, kind, a, spos);
-        if (r.sp.alignment) tap_row(gi, n, T - 1 - T3_COND_ROWS);      // this row's logits draw token n
+        if (r.sp.alignment) tap_row(gi, n, T - 1 - T3_COND_ROWS, r.sp.alignment == 2);      // this row's logits draw token n
         hm.sel_rows[2 * sr.n_sel + 1] = sr.M; add_row(gi, 2 * r.slot + 1, pos, kind, a, spos);
         hm.sel[sr.n_sel] = make_int4(r.slot, n, 0, 0);
         sr.sum_ctx += 2.0 * (pos + 1);
@@ -768,7 +787,7 @@ static int build_step(T3Engine* e, T3Engine::Step& st, bool may_admit) {
                 else if (p < T - 1) { if (sI == 0) add_row(gi, 2 * r.slot, p, EMB_TEXT, r.prompt[p], p - T3_COND_ROWS); else add_row(gi, 2 * r.slot + 1, p, EMB_ZERO, 0, 0); }
                 else add_row(gi, 2 * r.slot + sI, p, EMB_SPEECH, 6561, 0);      // BOS: speech_emb[start] + speech_pos[0], t3.py:550-551
                 if (p == T - 1) hm.sel_rows[2 * sr.n_sel + sI] = sr.M - 1;
-                if (p == T - 1 && sI == 0 && r.sp.alignment) tap_row(gi, 0, T - 1 - T3_COND_ROWS);      // the BOS row draws token 0
+                if (p == T - 1 && sI == 0 && r.sp.alignment) tap_row(gi, 0, T - 1 - T3_COND_ROWS, r.sp.alignment == 2);      // the BOS row draws token 0
             }
         r.n_prefilled = p1; sr.n_prefill_rows += 2 * chunk; sr.max_prefill_ctx = std::max(sr.max_prefill_ctx, p1);
         if (p1 == T) {
@@ -818,7 +837,7 @@ static int launch_steps(T3Engine* e, T3Engine::Step* steps, int n) {
             for (int r = 0; r < sr.M; ++r) { const int* rec = g.hm[buf].rows + (size_t)r * e->row_stride; e->dbg_emb_rec[2 * r] = rec[0]; e->dbg_emb_rec[2 * r + 1] = rec[1]; }
         }
         if (graphs_ok) {
-            const auto key = std::make_tuple(sr.M, sr.n_sel, e->zero_copy ? buf : 0, n, sr.tapped);      // zero-copy: the pinned buffers of `buf` ... are kernel arguments
+            const auto key = std::make_tuple(sr.M, sr.n_sel, e->zero_copy ? buf : 0, n, (int)sr.tapped + 2 * (int)sr.guarded);      // zero-copy: the pinned buffers of `buf` ... are kernel arguments
             auto it = g.graphs.find(key);
             if (it == g.graphs.end()) {
                 hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
@@ -951,6 +970,14 @@ static int complete_step(T3Engine* e, T3Engine::Step& st, T3StepResult* res, dou
                         r.align_ld = e->align_ld;
                         ce = hipMemcpyAsync(r.d_align, e->d_align + (size_t)r.slot * e->cfg.max_model_len * e->align_ld, bytes, hipMemcpyDeviceToDevice, e->groups[gi].stream);
                         if (ce != hipSuccess && !dev_rc) dev_rc = e->fail(T3_E_DEVICE, std::string("copy of a finished request's alignment matrix failed: ") + hipGetErrorString(ce));
+                        if (r.sp.alignment == 2) {
+                            // its guard state rides in the buffer's last words: a matrix has at most max_model_len - 35 rows, so the last 35 rows of the
+                            // buffer are never frames.  The steps still in flight behind the stop id leave the state alone (t3_guard.hip)
+                            ce = hipMemcpyAsync(r.d_align + cap / 4 - GUARD_STATE_WORDS, e->d_guard_state + (size_t)r.slot * GUARD_STATE_WORDS, GUARD_STATE_WORDS * 4,
+                                                hipMemcpyDeviceToDevice, e->groups[gi].stream);
+                            if (ce != hipSuccess && !dev_rc) dev_rc = e->fail(T3_E_DEVICE, std::string("copy of a finished request's guard state failed: ") + hipGetErrorString(ce));
+                            r.has_guard = ce == hipSuccess;
+                        }
                     }
                 }
                 if (res->n_finished < 64) res->finished_ids[res->n_finished] = r.id;
@@ -1180,6 +1207,51 @@ extern "C" int t3_get_alignment(T3Handle e, int64_t req_id, float* out, int32_t*
     std::vector<float> rows((size_t)nf * r.align_ld);
     HIP_TRY(hipMemcpy(rows.data(), r.d_align, rows.size() * 4, hipMemcpyDeviceToHost));
     for (int k = 0; k < nf; ++k) memcpy(out + (size_t)k * nt, rows.data() + (size_t)k * r.align_ld, (size_t)nt * 4);
+    return T3_OK;
+}
+
+// ---- alignment guard ---------------------------------------------------------------------------------
+extern "C" int t3_set_alignment_guard(T3Handle e, const T3GuardParams* params) {
+    if (!e) return T3_E_INVALID;
+    T3GuardParams p{(int32_t)sizeof(T3GuardParams), 4, 7, 3, 5, 5.0f, 5.0f, 3};
+    if (params) {
+        if (params->struct_size != (int32_t)sizeof(T3GuardParams)) return e->fail(T3_E_INVALID, "T3GuardParams.struct_size is not sizeof(T3GuardParams)");
+        const T3GuardParams& q = *params;
+        const bool zeroed = !q.back && !q.fwd && !q.end && !q.skip && q.tail_thr == 0.0f && q.rep_thr == 0.0f && !q.tok_rep;
+        if (!zeroed) p = q;
+        if (p.back < 1 || p.fwd < 1 || p.end < 0 || p.skip < 0 || p.tok_rep < 0 || p.tok_rep > 16 ||
+            !(p.tail_thr >= 0.0f && p.tail_thr <= 3.0e38f) || !(p.rep_thr >= 0.0f && p.rep_thr <= 3.0e38f))
+            return e->fail(T3_E_INVALID, "T3GuardParams out of range: back, fwd >= 1; end, skip >= 0; tok_rep in [0, 16]; thresholds finite and >= 0");
+    }
+    if (!e->running.empty() || !e->waiting.empty()) return e->fail(T3_E_STATE, "t3_set_alignment_guard while requests are queued or running");
+    (void)hipSetDevice(e->cfg.device_id);
+    int rc;
+    if ((rc = drop_graphs(e))) return rc;      // they carry the guard launch, its parameters and the sampler's instantiation
+    if (!params) {
+        free_dev(e->d_guard_state); free_dev(e->d_guard_ctl); e->d_guard_state = nullptr; e->d_guard_ctl = nullptr;
+        return T3_OK;
+    }
+    if (!e->d_guard_state) {
+        if ((rc = dalloc(e, &e->d_guard_state, (size_t)e->cfg.max_seqs * GUARD_STATE_WORDS, true))) { e->d_guard_state = nullptr; return rc; }
+        if ((rc = dalloc(e, &e->d_guard_ctl, (size_t)e->cfg.max_seqs, true))) { free_dev(e->d_guard_state); e->d_guard_state = nullptr; e->d_guard_ctl = nullptr; return rc; }
+    }
+    e->guard = p;
+    return T3_OK;
+}
+
+extern "C" int t3_get_guard(T3Handle e, int64_t req_id, T3GuardState* out) {
+    if (!e || !out) return T3_E_INVALID;
+    auto it = e->reqs.find(req_id);
+    if (it == e->reqs.end()) return e->fail(T3_E_NOTFOUND, "unknown request id");
+    const Request& r = it->second;
+    if (r.sp.alignment != 2) return e->fail(T3_E_INVALID, "request " + std::to_string(req_id) + " was not submitted with alignment = 2");
+    if (r.state != FINISHED) return e->fail(T3_E_STATE, "request " + std::to_string(req_id) + " has not finished");
+    if (!r.d_align || !r.has_guard) return e->fail(T3_E_DEVICE, "the guard state of request " + std::to_string(req_id) + " could not be kept");
+    (void)hipSetDevice(e->cfg.device_id);
+    for (auto& g : e->groups) if (g.stream) HIP_TRY(hipStreamSynchronize(g.stream));      // the copy-out was queued on a group stream
+    int words[GUARD_STATE_WORDS];
+    HIP_TRY(hipMemcpy(words, r.d_align + (size_t)e->cfg.max_model_len * r.align_ld - GUARD_STATE_WORDS, sizeof(words), hipMemcpyDeviceToHost));
+    guard_unpack_state(words, out);
     return T3_OK;
 }
 

@@ -324,7 +324,7 @@ extern "C" int t3k_decode_attention_fp8(const void* ctx_qkv, int32_t n_content, 
 }
 
 static int sample_impl(const void* logits2, int32_t ldl, uint16_t* counts, const T3Sampling* sp, float cfg, uint32_t step,
-                       int32_t* token_out, float* logits_out, uint8_t* keep_out);
+                       int32_t* token_out, float* logits_out, uint8_t* keep_out, int32_t ctl = -1);
 extern "C" int t3k_sample(const void* logits2, int32_t ldl, uint16_t* counts, const T3Sampling* sp, float cfg, uint32_t step,
                           int32_t* token_out, float* logits_out) { return sample_impl(logits2, ldl, counts, sp, cfg, step, token_out, logits_out, nullptr); }
 /* t3k_sample + the SUPPORT of the draw: keep_out [8194] = 1 where the masks (penalties -> /T -> min-p -> top-k -> top-p) leave the id drawable */
@@ -333,9 +333,17 @@ extern "C" int t3k_sample_support(const void* logits2, int32_t ldl, uint16_t* co
     if (!keep_out) return T3_E_INVALID;
     return sample_impl(logits2, ldl, counts, sp, cfg, step, token_out, nullptr, keep_out);
 }
-static int sample_impl(const void* logits2, int32_t ldl, uint16_t* counts, const T3Sampling* sp, float cfg, uint32_t step,
-                       int32_t* token_out, float* logits_out, uint8_t* keep_out) {
-    if (!logits2 || !counts || !sp || !token_out || ldl < V) return T3_E_INVALID;
+/* the sampler's guarded instantiation under one control word: the slot is marked guarded (alignment = 2) in the kernel's copy of sp */
+extern "C" int t3k_sample_ctl(const void* logits2, int32_t ldl, uint16_t* counts, const T3Sampling* sp, float cfg, uint32_t step, int32_t ctl,
+                              int32_t* token_out, float* logits_out) {
+    if (ctl < GUARD_NONE || ctl > GUARD_FORCE || !sp || sp->stop_token < 0 || sp->stop_token >= V) return T3_E_INVALID;
+    return sample_impl(logits2, ldl, counts, sp, cfg, step, token_out, logits_out, nullptr, ctl);
+}
+static int sample_impl(const void* logits2, int32_t ldl, uint16_t* counts, const T3Sampling* sp_in, float cfg, uint32_t step,
+                       int32_t* token_out, float* logits_out, uint8_t* keep_out, int32_t ctl) {
+    if (!logits2 || !counts || !sp_in || !token_out || ldl < V) return T3_E_INVALID;
+    T3Sampling sp_copy = *sp_in; const T3Sampling* sp = &sp_copy;
+    if (ctl >= 0) sp_copy.alignment = 2;
     if (!have_device()) return T3_E_DEVICE;
     std::vector<uint16_t> cpad(VPAD, 0);
     memcpy(cpad.data(), counts, V * 2);
@@ -344,6 +352,8 @@ static int sample_impl(const void* logits2, int32_t ldl, uint16_t* counts, const
     K_TRY(dl.from(logits2, (size_t)2 * ldl * 2)); K_TRY(dc.from(cpad.data(), VPAD * 2)); K_TRY(dsp.from(sp, sizeof(T3Sampling)));
     K_TRY(dsel.from(&sel, sizeof(sel))); K_TRY(dtok.alloc(4, true)); K_TRY(ddbg.alloc((size_t)V * 4, true));
     SampleArgs sa{dl.as<uint16_t>(), ldl, dsel.as<int4>(), dc.as<uint16_t>(), dsp.as<T3Sampling>(), cfg, dtok.as<int>(), ddbg.as<float>(), 1};
+    DevBuf dctl;
+    if (ctl >= 0) { K_TRY(dctl.from(&ctl, 4)); sa.eos_ctl = dctl.as<int>(); }
     DevBuf dkeep;
     if (keep_out) { K_TRY(dkeep.alloc(V, true)); sa.dbg_keep = dkeep.as<unsigned char>(); }
     K_TRY(launch_sampler(sa, nullptr));
@@ -390,5 +400,37 @@ extern "C" int t3k_expf(const float* x, float* y, int32_t n) {
     K_TRY(launch_expf(dx.as<float>(), dy.as<float>(), n, nullptr));
     K_TRY(hipDeviceSynchronize());
     K_TRY(hipMemcpy(y, dy.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return T3_OK;
+}
+
+/* The guard kernel (t3_guard.hip) frame by frame over a host matrix: slot 0, frame k = launch k, the ids as the sampler's history. */
+extern "C" int t3k_alignment_guard(const float* A, int32_t n_frames, int32_t n_text, int32_t ld, const int32_t* tok, const T3GuardParams* params,
+                                   int32_t* ctl_out, T3GuardState* final_state) {
+    if (!A || !tok || !params || !ctl_out || !final_state || n_frames <= 0 || n_text <= 0 || ld < n_text || (ld & 3)) return T3_E_INVALID;
+    for (int k = 0; k < n_frames; ++k) if (tok[k] < 0) return T3_E_INVALID;
+    if (!have_device()) return T3_E_DEVICE;
+    const int stride = row_stride_words(1);
+    std::vector<int> recs((size_t)n_frames * stride, 0);
+    std::vector<int4> sel(n_frames);
+    for (int k = 0; k < n_frames; ++k) {
+        recs[(size_t)k * stride + ROW_ALIGN_FRAME] = k; recs[(size_t)k * stride + ROW_ALIGN_NTEXT] = n_text;
+        sel[k] = make_int4(0, k, 0, 0);
+    }
+    T3Sampling sp{}; sp.alignment = 2; sp.stop_token = -1;      // no id ends the utterance here
+    DevBuf dA, dtok, drec, dsel, dsp, dstate, dctl;
+    K_TRY(dA.from(A, (size_t)n_frames * ld * 4)); K_TRY(dtok.from(tok, (size_t)n_frames * 4)); K_TRY(drec.from(recs.data(), recs.size() * 4));
+    K_TRY(dsel.from(sel.data(), sel.size() * sizeof(int4))); K_TRY(dsp.from(&sp, sizeof(sp)));
+    K_TRY(dstate.alloc(GUARD_STATE_WORDS * 4)); K_TRY(dctl.alloc((size_t)n_frames * 4, true));
+    K_TRY(launch_guard_reset(dstate.as<int>(), dctl.as<int>(), 0, nullptr));
+    for (int k = 0; k < n_frames; ++k) {      // launch k: its record, its sel entry, its own control word
+        GuardArgs ga{dA.as<float>(), n_frames, ld, drec.as<int>() + (size_t)k * stride, stride, nullptr, dsel.as<int4>() + k, dsp.as<T3Sampling>(),
+                     dtok.as<int>(), n_frames, dstate.as<int>(), dctl.as<int>() + k, 1, *params};
+        K_TRY(launch_guard(ga, nullptr));
+    }
+    K_TRY(hipDeviceSynchronize());
+    int words[GUARD_STATE_WORDS];
+    K_TRY(hipMemcpy(words, dstate.p, sizeof(words), hipMemcpyDeviceToHost));
+    K_TRY(hipMemcpy(ctl_out, dctl.p, (size_t)n_frames * 4, hipMemcpyDeviceToHost));
+    guard_unpack_state(words, final_state);
     return T3_OK;
 }

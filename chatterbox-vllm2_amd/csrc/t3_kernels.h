@@ -71,7 +71,7 @@ void set_pgemm_wide_rows(int rows);  // row count from which its 4-segment forms
 // Per-row record of a step (int32 words), built by the scheduler and uploaded once per step:
 //   [0] stream  [1] position  [2] embed kind  [3] embed a  [4] embed b  [5] alignment frame  [6] alignment n_text  [7] unused  [8 ..] KV block ids of the row's stream
 // One lookup gives a kernel everything it needs to address the row's paged KV (no stream -> block-table hop).
-// [5], [6]: read by the alignment tap only (t3_alignment.hip).  frame = index of the token this row's logits produce, -1 = the row is not
+// [5], [6]: read by the alignment tap and the guard only (t3_alignment.hip, t3_guard.hip). frame = index of the token this row's logits produce, -1 = the row is not
 // tapped; n_text = text ids of its prompt.
 constexpr int ROW_HDR = 8;
 constexpr int ROW_ALIGN_FRAME = 5, ROW_ALIGN_NTEXT = 6;
@@ -162,8 +162,31 @@ struct SampleArgs {
     int hist_cap = 0;
     int* out_tok_host = nullptr;   // nullable: [n] in pinned host memory, written beside out_tok (no copy kernel behind the step)
     unsigned char* dbg_keep = nullptr;   // nullable (parity hook t3k_sample_support): [max_seqs][V] 1 where the draw can return the id
+    const int* eos_ctl = nullptr;  // nullable: [max_seqs] guard control words (t3_guard.hip), obeyed for the slots whose sp.alignment is 2.  Non-null
+                                   // launches the sampler's guarded instantiation; null launches the kernel as it was before the guard existed
 };
 hipError_t launch_sampler(const SampleArgs& a, hipStream_t s);
+
+// The alignment guard (t3_guard.hip): one wave per sampled utterance reads the frame the step's taps have just completed, moves the slot's
+// state (include/t3_engine.h spells the rules out) and leaves the control word the step's sampler obeys.
+constexpr int GUARD_NONE = 0, GUARD_SUPPRESS = 1, GUARD_FORCE = 2;
+constexpr int GUARD_STATE_WORDS = 8;   // pos | complete + 256 reason | completed_at | forced_at + 1 | tail[3] (fp32) | rep (fp32): all zero = admitted
+struct GuardArgs {
+    const float* frames;       // [max_seqs][frames_per_slot][ld]: the alignment frames (AlignArgs.out)
+    int frames_per_slot, ld;
+    const int* rowrec; int row_stride;
+    const int* sel_rows;       // nullable: wave u serves row sel_rows[2 u] (null: row u)
+    const int4* sel;           // per sampled utterance {slot, step, 0, 0}
+    const T3Sampling* sp;      // [max_seqs]: alignment == 2 marks a guarded slot, stop_token ends its utterance
+    const int* hist; int hist_cap;      // the sampler's history (SampleArgs.hist)
+    int* state;                // [max_seqs][GUARD_STATE_WORDS]
+    int* ctl;                  // [max_seqs]
+    int n_sel;
+    T3GuardParams p;
+};
+hipError_t launch_guard(const GuardArgs& a, hipStream_t s);
+hipError_t launch_guard_reset(int* state, int* ctl, int slot, hipStream_t s);   // the slot's state and control word = 0, by a kernel
+void guard_unpack_state(const int* words, T3GuardState* out);                  // host: state words -> the ABI's struct
 // Profile mode: the next single-kernel launch of this thread (decode GEMM forms, fused / per-row attention, embed, sampler) takes these as
 // its start / stop events (hipExtLaunchKernelGGL); launch_events_armed() afterwards tells whether a launcher consumed them.
 void arm_launch_events(hipEvent_t start, hipEvent_t stop);

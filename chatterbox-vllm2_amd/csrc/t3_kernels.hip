@@ -195,6 +195,10 @@ __device__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3
 #else
 #define T3_CLK(i)
 #endif
+// CTL: the guarded instantiation (SampleArgs.eos_ctl, t3_guard.hip).  A slot whose sp.alignment is 2 obeys its control word: GUARD_FORCE draws the
+// stop id whatever the logits hold (history and counts written as for any id), GUARD_SUPPRESS puts the stop id's post-CFG logit at -inf in front
+// of the penalties and everything behind them.  CTL = false compiles to the kernel as it was before the guard existed.
+template <bool CTL>
 __global__ __launch_bounds__(STH) void sampler_kernel(SampleArgs a) {
 #ifdef T3_SAMPLER_CLK
     unsigned long long clk[12] = {0};
@@ -234,6 +238,12 @@ __global__ __launch_bounds__(STH) void sampler_kernel(SampleArgs a) {
 #endif
     };
 
+    int suppress = -1;                                   // CTL: the id whose logit is -inf this step
+    if constexpr (CTL) {
+        const int ctl = sp.alignment == 2 ? a.eos_ctl[slot] : GUARD_NONE;
+        if (ctl == GUARD_FORCE) { if (tid == 0) finish(sp.stop_token); return; }
+        if (ctl == GUARD_SUPPRESS) suppress = sp.stop_token;
+    }
     // ---- phase A: CFG, penalties.  16-byte loads of 8 logits / counts, all issued before the first use
     // (a scalar loop here is a chain of dependent memory latencies, not bandwidth).
     const bool greedy = sp.temperature < 1e-5f;
@@ -268,6 +278,7 @@ __global__ __launch_bounds__(STH) void sampler_kernel(SampleArgs a) {
             const float d = rbf(c - un);
             const float e = rbf(a.cfg * d);
             x = rbf(c + e);
+            if constexpr (CTL) { if (v == suppress) x = -INFINITY; }
             if (a.dbg) a.dbg[(size_t)slot * V + v] = x;
             if (cnt > 0) {
                 if (sp.repetition_penalty != 1.0f) x = (x > 0.0f) ? x / sp.repetition_penalty : x * sp.repetition_penalty;
@@ -522,7 +533,8 @@ hipError_t prepare_kernels() {
     static bool done[MAX_DEVICES] = {};
     if (done[cur_device()]) return hipSuccess;
     const size_t lds = (size_t)(SLOTS / 2 + SSCR + 6 * 256) * sizeof(unsigned long long);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(sampler_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(sampler_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(sampler_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e == hipSuccess) e = prepare_gemm2();
     if (e == hipSuccess) done[cur_device()] = true;
     return e;
@@ -532,7 +544,8 @@ hipError_t launch_sampler(const SampleArgs& a, hipStream_t s) {
     const size_t lds = (size_t)(SLOTS / 2 + SSCR + 6 * 256) * sizeof(unsigned long long);
     hipError_t e = prepare_kernels();
     if (e != hipSuccess) return e;
-    launch_k(sampler_kernel, dim3(a.n), dim3(STH), lds, s, a);
+    if (a.eos_ctl) launch_k(sampler_kernel<true>, dim3(a.n), dim3(STH), lds, s, a);
+    else launch_k(sampler_kernel<false>, dim3(a.n), dim3(STH), lds, s, a);
     return hipGetLastError();
 }
 

@@ -40,6 +40,41 @@ class T3Sampling(ct.Structure):
     ]
 
 
+class T3GuardParams(ct.Structure):
+    _fields_ = [("struct_size", ct.c_int32), ("back", ct.c_int32), ("fwd", ct.c_int32), ("end", ct.c_int32), ("skip", ct.c_int32),
+                ("tail_thr", ct.c_float), ("rep_thr", ct.c_float), ("tok_rep", ct.c_int32)]
+
+
+class T3GuardState(ct.Structure):
+    _fields_ = [("pos", ct.c_int32), ("complete", ct.c_int32), ("completed_at", ct.c_int32), ("forced_at", ct.c_int32), ("reason", ct.c_int32),
+                ("tail", ct.c_float * 3), ("rep", ct.c_float)]
+
+
+# The alignment guard's parameters (include/t3_engine.h).  They follow upstream's AlignmentStreamAnalyzer as its rules are known to the
+# maintainers and have not been validated against a real checkpoint on this project.
+GUARD_DEFAULTS = dict(back=4, fwd=7, end=3, skip=5, tail_thr=5.0, rep_thr=5.0, tok_rep=3)
+GUARD_REASONS = {0: None, 1: "token_repetition", 2: "long_tail", 3: "alignment_repetition"}
+
+
+def make_guard_params(overrides=None) -> T3GuardParams:
+    """True / None / {} = the defaults; a dict overrides some of them.  An unknown name is a ValueError."""
+    kw = dict(GUARD_DEFAULTS)
+    if isinstance(overrides, dict):
+        unknown = sorted(set(overrides) - set(kw))
+        if unknown:
+            raise ValueError(f"alignment_guard: unknown parameter(s) {unknown}; the guard has {sorted(kw)}")
+        kw.update(overrides)
+    elif overrides not in (None, True):
+        raise ValueError("alignment_guard is True or a dict of parameter overrides")
+    return T3GuardParams(ct.sizeof(T3GuardParams), int(kw["back"]), int(kw["fwd"]), int(kw["end"]), int(kw["skip"]),
+                         float(kw["tail_thr"]), float(kw["rep_thr"]), int(kw["tok_rep"]))
+
+
+def guard_state_dict(st: T3GuardState) -> dict:
+    return dict(pos=st.pos, complete=bool(st.complete), completed_at=st.completed_at, forced_at=st.forced_at, reason=GUARD_REASONS.get(st.reason),
+                tail=[float(x) for x in st.tail], rep=float(st.rep))
+
+
 class T3StepResult(ct.Structure):
     _fields_ = [
         ("n_rows", ct.c_int32), ("n_prefill_rows", ct.c_int32), ("n_sampled", ct.c_int32), ("n_finished", ct.c_int32),
@@ -65,6 +100,7 @@ ABI_SYMBOLS = [
     "t3k_gemm", "t3k_norm_gemm", "t3k_qkv_gemm", "t3k_head_gemm", "t3k_gemm_resid", "t3k_silu_mul_gemm", "t3k_rope_attention", "t3k_decode_attention", "t3k_sample", "t3k_sample_support", "t3k_expf",
     "t3k_fp8_roundtrip", "t3k_rope_attention_fp8", "t3k_decode_attention_fp8",
     "t3_reserve_alignment", "t3_set_alignment_heads", "t3_get_alignment", "t3k_attention_probs",
+    "t3_set_alignment_guard", "t3_get_guard", "t3k_alignment_guard", "t3k_sample_ctl",
     "t3_cond_create", "t3_cond_destroy", "t3_cond_last_error", "t3_cond_load_tensor", "t3_cond_encode", "t3_cond_emotion_row",
     "t3k_ce_layernorm", "t3k_ce_linear", "t3k_ce_attention", "t3k_set_prefill_rows", "t3k_set_prefill_wide_rows",
 ]
@@ -138,6 +174,10 @@ def load_library():
     L.t3_set_alignment_heads.argtypes = [vp, vp, i32]
     L.t3_get_alignment.argtypes = [vp, i64, vp, ct.POINTER(i32), ct.POINTER(i32)]
     L.t3k_attention_probs.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]
+    L.t3_set_alignment_guard.argtypes = [vp, ct.POINTER(T3GuardParams)]
+    L.t3_get_guard.argtypes = [vp, i64, ct.POINTER(T3GuardState)]
+    L.t3k_alignment_guard.argtypes = [vp, i32, i32, i32, vp, ct.POINTER(T3GuardParams), vp, ct.POINTER(T3GuardState)]
+    L.t3k_sample_ctl.argtypes = [vp, i32, vp, ct.POINTER(T3Sampling), ct.c_float, ct.c_uint32, i32, vp, vp]
     L.t3_cond_create.argtypes = [i32, ct.POINTER(vp)]
     L.t3_cond_destroy.argtypes = [vp]
     L.t3_cond_last_error.restype = ct.c_char_p; L.t3_cond_last_error.argtypes = [vp]
@@ -171,10 +211,12 @@ def _raise(code: int, msg: str):
 
 def make_sampling(temperature=0.8, top_p=1.0, min_p=0.0, repetition_penalty=2.0, presence_penalty=0.0,
                   frequency_penalty=0.0, top_k=0, max_tokens=1000, ignore_eos=False,
-                  stop_token=C.STOP_SPEECH_TOKEN, seed=0, uid=0, pos_policy=0, alignment=False) -> T3Sampling:
+                  stop_token=C.STOP_SPEECH_TOKEN, seed=0, uid=0, pos_policy=0, alignment=False, alignment_guard=False) -> T3Sampling:
+    """alignment_guard=True: tap plus guard (T3Sampling.alignment = 2); the engine's guard must be enabled (T3Engine.set_alignment_guard)."""
     return T3Sampling(float(temperature), float(top_p), float(min_p), float(repetition_penalty),
                       float(presence_penalty), float(frequency_penalty), int(top_k), int(max_tokens),
-                      int(bool(ignore_eos)), int(stop_token), int(seed), int(uid), int(pos_policy), int(bool(alignment)))
+                      int(bool(ignore_eos)), int(stop_token), int(seed), int(uid), int(pos_policy),
+                      2 if alignment_guard else int(bool(alignment)))
 
 
 # storage formats of the paged KV pool (T3EngineConfig.kv_cache_dtype), under vLLM's names for them
@@ -205,6 +247,7 @@ class T3Engine:
                                   int(kv_bytes), float(gpu_memory_utilization), float(cfg_scale),
                                   int(enforce_eager), int(debug_logits), int(n_groups), kv_code)
         self.alignment_max_text = 0       # text ids the alignment frames are reserved for (reserve_alignment)
+        self.guard_params = None          # the enabled guard's parameters as a dict (set_alignment_guard), None = disabled
         self.h = ct.c_void_p()
         rc = self.lib.t3_create(ct.byref(self.cfg), ct.byref(self.h))
         if rc:
@@ -327,6 +370,25 @@ class T3Engine:
         out = torch.zeros(int(nf.value), int(nt.value), dtype=torch.float32)
         self._chk(self.lib.t3_get_alignment(self.h, int(req_id), ct.c_void_p(out.data_ptr()), ct.byref(nf), ct.byref(nt)))
         return out
+
+    def set_alignment_guard(self, params=True):
+        """Enable the alignment guard (True = default parameters, or a dict of overrides) or, with None / False, disable it.  Only while
+        nothing is queued or running.  Requests made with make_sampling(alignment_guard=True) are then held back from, or forced to, their
+        stop token on the device (csrc/t3_guard.hip)."""
+        if params is None or params is False:
+            self._chk(self.lib.t3_set_alignment_guard(self.h, None))
+            self.guard_params = None
+            return
+        p = make_guard_params(params)
+        self._chk(self.lib.t3_set_alignment_guard(self.h, ct.byref(p)))
+        self.guard_params = {k: getattr(p, k) for k in GUARD_DEFAULTS}
+
+    def get_guard(self, req_id: int) -> dict:
+        """The final guard state of a finished, unreleased guarded request: pos, complete, completed_at, forced_at (-1: never), reason (None,
+        'token_repetition', 'long_tail', 'alignment_repetition'), tail [3], rep."""
+        st = T3GuardState()
+        self._chk(self.lib.t3_get_guard(self.h, int(req_id), ct.byref(st)))
+        return guard_state_dict(st)
 
     def pop_finished(self, cap: int = 4096) -> List[int]:
         """ids of the requests that finished since the last call, oldest first"""
@@ -483,6 +545,28 @@ def k_attention_probs(qkv: torch.Tensor, row_stream, row_pos, n_streams: int, ma
     _chk_k(load_library().t3k_attention_probs(qkv.data_ptr(), rs.ctypes.data, rp.ctypes.data, rows, n_streams, max_pos, int(head), int(lo), int(hi),
                                               kv_cache_dtype_code(kv_dtype), out.data_ptr(), q.data_ptr(), kv.data_ptr()), "t3k_attention_probs")
     return out, q, kv
+
+
+def k_alignment_guard(A: torch.Tensor, n_text: int, tok, params=None):
+    """The guard kernel frame by frame over A [n_frames, ld] fp32 (columns >= n_text are padding) and the drawn ids tok [n_frames]
+    -> (control word per frame [n_frames] as a list: 0 nothing, 1 suppress, 2 force; final state dict)."""
+    A = A.to(torch.float32).contiguous()
+    t = np.ascontiguousarray(np.asarray(tok, dtype=np.int32))
+    n = A.shape[0]
+    assert len(t) == n
+    ctl = np.zeros(n, dtype=np.int32); st = T3GuardState(); p = make_guard_params(params)
+    _chk_k(load_library().t3k_alignment_guard(A.data_ptr(), n, int(n_text), A.shape[1], t.ctypes.data, ct.byref(p), ctl.ctypes.data, ct.byref(st)), "t3k_alignment_guard")
+    return ctl.tolist(), guard_state_dict(st)
+
+
+def k_sample_ctl(logits2: torch.Tensor, counts: torch.Tensor, sp: T3Sampling, cfg: float, step: int, ctl: int) -> int:
+    """k_sample under a guard control word (0 nothing, 1 suppress sp.stop_token, 2 force it) -> token"""
+    logits2 = _bf(logits2)
+    assert counts.dtype == torch.uint16 and counts.numel() == C.SPEECH_VOCAB
+    tok = ct.c_int32(0)
+    _chk_k(load_library().t3k_sample_ctl(logits2.data_ptr(), logits2.shape[1], counts.data_ptr(), ct.byref(sp), ct.c_float(cfg),
+                                         ct.c_uint32(step), int(ctl), ct.byref(tok), None), "t3k_sample_ctl")
+    return int(tok.value)
 
 
 def k_fp8_roundtrip(x: torch.Tensor) -> torch.Tensor:

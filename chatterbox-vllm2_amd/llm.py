@@ -20,7 +20,7 @@ from typing import Any, Dict, List, Optional, Sequence, Union
 import torch
 
 from . import constants as C
-from .engine import T3Engine, kv_cache_dtype_code, make_sampling
+from .engine import T3Engine, kv_cache_dtype_code, make_guard_params, make_sampling
 from .prompt import TextTokenizer, assemble_prompt_ids, find_tokenizer_file
 from .weights import iter_safetensors, synthetic_tensors
 
@@ -36,7 +36,8 @@ class SamplingParams:
     def __init__(self, n: int = 1, temperature: float = 1.0, top_p: float = 1.0, top_k: int = 0, min_p: float = 0.0,
                  repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
                  seed: Optional[int] = None, stop_token_ids: Optional[List[int]] = None, max_tokens: Optional[int] = 16,
-                 ignore_eos: bool = False, pos_policy: int = 0, alignment: bool = False, **kwargs):
+                 ignore_eos: bool = False, pos_policy: int = 0, alignment: bool = False,
+                 alignment_guard: Union[bool, dict, None] = False, **kwargs):
         for k, v in kwargs.items():
             if k not in self._IGNORED:
                 raise TypeError(f"SamplingParams got an unexpected keyword argument {k!r}")
@@ -63,6 +64,18 @@ class SamplingParams:
         # extension: keep the text-speech alignment matrix of the request (CompletionOutput.alignment) -- what upstream's
         # AlignmentStreamAnalyzer reads from its attention hooks and a vLLM engine cannot hand out
         self.alignment = bool(alignment)
+        # extension: the on-device alignment guard (csrc/t3_guard.hip) holds the stop token back until the text is spoken and forces it once
+        # the model lingers on, or goes back over, spoken text.  True = the default parameters, a dict overrides some (engine.GUARD_DEFAULTS;
+        # not validated against a real checkpoint).  Implies alignment=True; CompletionOutput.guard reports the final state.
+        self.alignment_guard = None
+        if alignment_guard not in (None, False):
+            make_guard_params(alignment_guard)        # ValueError for an unknown name or a wrong type
+            if ignore_eos:
+                raise ValueError("alignment_guard cannot be combined with ignore_eos: the guard works by drawing the stop token")
+            if not stop_token_ids:
+                raise ValueError("alignment_guard needs stop_token_ids: the token the guard suppresses or forces")
+            self.alignment_guard = dict(alignment_guard) if isinstance(alignment_guard, dict) else {}
+            self.alignment = True
 
     def __repr__(self):
         return ("SamplingParams(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in (
@@ -79,6 +92,7 @@ class CompletionOutput:
     finish_reason: Optional[str] = None
     stop_reason: Union[int, str, None] = None
     alignment: Optional[torch.Tensor] = None      # SamplingParams(alignment=True): CPU float32 [n_tokens, n_text], row k = frame k's attention over the text
+    guard: Optional[dict] = None                  # SamplingParams(alignment_guard=...): the guard's final state (T3Engine.get_guard); reason None = never forced
 
 
 @dataclass
@@ -101,7 +115,8 @@ class LLM:
                  max_num_batched_tokens: int = 0, seed: int = 0, load_format: str = "auto", dtype: str = "bfloat16",
                  device_id: Optional[int] = None, tokenizer_file: Optional[str] = None, num_hidden_layers: Optional[int] = None,
                  kv_cache_bytes: int = 0, debug_logits: bool = False, honor_enforce_eager: Optional[bool] = None,
-                 kv_cache_dtype: Optional[str] = None, alignment_max_text: int = 0, **kwargs):
+                 kv_cache_dtype: Optional[str] = None, alignment_max_text: int = 0,
+                 alignment_guard: Union[bool, dict, None] = None, **kwargs):
         if task != "generate":
             raise ValueError("only task='generate' exists on the T3 path")
         if dtype not in ("bfloat16", "auto", torch.bfloat16):
@@ -146,6 +161,10 @@ class LLM:
         # request reserves for the longest text of that call
         if alignment_max_text > 0:
             self.engine.reserve_alignment(alignment_max_text)
+        # alignment guard: enabled now with these parameters (True = defaults); None = the first generate() with a guarded request enables it
+        # with that call's parameters
+        if alignment_guard not in (None, False):
+            self.engine.set_alignment_guard(alignment_guard)
         tf = find_tokenizer_file(self.tokenizer_kind, model if model and os.path.isdir(model) else None, tokenizer_file)
         self.tokenizer = TextTokenizer(self.tokenizer_kind, tf) if tf else None
         self._next_id = 0
@@ -223,15 +242,16 @@ class LLM:
             if keep_for_handoff and not kept_before:
                 self.engine.reserve_handoff(0)      # finished requests keep the buffers they hold; no new ones are made
         outs = []
-        for rid, text, final, tap in metas:
+        for rid, text, final, tap, guarded in metas:
             toks, fr = self.engine.get_output(rid)
             align = self.engine.get_alignment(rid) if tap else None
+            guard = self.engine.get_guard(rid) if guarded else None
             if not keep_for_handoff:
                 self.engine.release(rid)
             reason = {1: "stop", 2: "length"}.get(fr)
             outs.append(RequestOutput(request_id=str(rid), prompt=text, prompt_token_ids=final,
                                       outputs=[CompletionOutput(index=0, text="", token_ids=toks, finish_reason=reason,
-                                                                stop_reason=(toks[-1] if fr == 1 else None), alignment=align)]))
+                                                                stop_reason=(toks[-1] if fr == 1 else None), alignment=align, guard=guard)]))
         return outs
 
     def handoff_tokens(self, outputs: Sequence[RequestOutput], text_token_counts: Sequence[int], range_filter: bool = True):
@@ -254,6 +274,14 @@ class LLM:
         tapped = [len(t[1]) for t, sp in zip(texts, sps) if sp.alignment]      # text ids per tapped request
         if tapped and max(tapped) > self.engine.alignment_max_text:
             self.engine.reserve_alignment(max(tapped))
+        guards = [sp.alignment_guard for sp in sps if sp.alignment_guard is not None]
+        if guards:
+            if any(g != guards[0] for g in guards):
+                raise ValueError("the guarded requests of one generate() call must share their alignment_guard parameters (one set per engine)")
+            if self.engine.guard_params is None:
+                self.engine.set_alignment_guard(guards[0])       # the first guarded call enables the guard with its parameters
+            elif any(self.engine.guard_params[k] != getattr(make_guard_params(guards[0]), k) for k in guards[0]):      # as the C struct rounds them
+                raise ValueError(f"alignment_guard {guards[0]} differs from the engine's enabled guard {self.engine.guard_params}")
         for i, ((text, tids, cond), sp) in enumerate(zip(texts, sps)):
             final = assemble_prompt_ids(tids)
             stop = -1
@@ -271,11 +299,12 @@ class LLM:
             esp = make_sampling(temperature=sp.temperature, top_p=sp.top_p, min_p=sp.min_p, repetition_penalty=sp.repetition_penalty,
                                 presence_penalty=sp.presence_penalty, frequency_penalty=sp.frequency_penalty,
                                 top_k=max(0, sp.top_k), max_tokens=max_tokens, ignore_eos=sp.ignore_eos, stop_token=stop,
-                                seed=self.seed if sp.seed is None else sp.seed, uid=uid, pos_policy=sp.pos_policy, alignment=sp.alignment)
+                                seed=self.seed if sp.seed is None else sp.seed, uid=uid, pos_policy=sp.pos_policy, alignment=sp.alignment,
+                                alignment_guard=sp.alignment_guard is not None)
             rid = self._next_id; self._next_id += 1
             self.engine.add_request(rid, final, cond, esp)
             queued.append(rid)
-            metas.append((rid, text, final, sp.alignment))
+            metas.append((rid, text, final, sp.alignment, sp.alignment_guard is not None))
 
     def shutdown(self):
         self.engine.close()

@@ -75,8 +75,9 @@ typedef struct {
     int32_t pos_policy;        /* 0: k-th generated token uses speech_pos_emb[k] (SURVEY.md 9 Q1 "exact");
                                   1: index 0 for every decode token (the literal fallback of t3.py:464) */
     int32_t alignment;         /* 1: keep the text-speech alignment matrix of this request (t3_get_alignment; needs t3_reserve_alignment);
-                                  0: off (default).  Any other value is T3_E_INVALID.  Token ids never depend on it.  This was padding: a C
-                                  caller must zero it */
+                                  2: the same, and the alignment guard reads every frame and suppresses or forces stop_token (needs
+                                  t3_set_alignment_guard, stop_token >= 0 and ignore_eos = 0); 0: off (default).  Any other value is
+                                  T3_E_INVALID.  Token ids never depend on it unless it is 2.  This was padding: a C caller must zero it */
 } T3Sampling;
 
 typedef struct {
@@ -200,6 +201,42 @@ int t3_set_alignment_heads(T3Handle h, const int32_t* layer_head_pairs, int32_t 
  * T3_E_INVALID; not finished: T3_E_STATE. */
 int t3_get_alignment(T3Handle h, int64_t req_id, float* out, int32_t* n_frames, int32_t* n_text);
 
+/* ---- alignment guard: EOS suppressed or forced on the device, from the alignment frames --------------------------------
+ * The logits half of upstream's AlignmentStreamAnalyzer, as a kernel inside the step (t3_guard.hip) and a sampler that obeys it.  For a request
+ * submitted with T3Sampling.alignment = 2, with S = n_text, a_k = row k of its alignment matrix and tok[k] the id drawn at step k, the state
+ * {pos, complete, completed_at, tail[3], rep, reason, forced_at = -1}, all zero at admission, moves at step k, before that step's sampler:
+ *   1. c = lowest index attaining max_t a_k[t], t < S.  -back < c - pos < fwd: pos = c; otherwise (a discontinuity) pos stays.
+ *   2. !complete and pos >= S - end: complete = 1, completed_at = k.
+ *   3. complete (this step included): tail[i] += a_k[S - 3 + i] for i < 3 with S - 3 + i >= 0;  rep += max(a_k[0 : S - skip]) (0 for an empty
+ *      range).  One fp32 add each per step, in step order.
+ *   4. long_tail = complete && max(tail) >= tail_thr;  align_rep = complete && rep > rep_thr;
+ *      tok_rep_hit = tok_rep > 0 && k >= tok_rep && tok[k-1] == ... == tok[k-tok_rep].
+ *   5. FORCE if one of them holds: reason = 1 token repetition, 2 long tail, 3 alignment repetition (the first in that order), forced_at = k;
+ *      the state is frozen from then on and every later step of the slot is forced too.  Otherwise SUPPRESS if pos < S - end && S > skip.
+ *      Otherwise nothing.
+ * SUPPRESS: the stop id's post-CFG logit is -inf in front of penalties, temperature, min-p, top-k and top-p, as if the caller had handed in the
+ * conditional logits with that column at -inf.  FORCE: the step's id is the stop id whatever the logits hold (NaN rows included); history and
+ * counts are written as for any drawn id, the request finishes with reason 1 and the stop id as its last token.  A step scheduled behind the
+ * one that drew the stop id (run-ahead, bursts) changes nothing: the state t3_get_guard returns is the state after the utterance's last step.
+ * The defaults follow upstream's analyzer as its rules are known to the maintainers; they have NOT been validated against a real checkpoint
+ * on this project, which is why every one of them is a parameter. */
+typedef struct {
+    int32_t struct_size;       /* sizeof(T3GuardParams).  Every other field 0: the defaults below; otherwise every field is taken as given */
+    int32_t back, fwd;         /* 4, 7: the window -back < c - pos < fwd inside which the position follows the argmax (both >= 1) */
+    int32_t end;               /* 3: the text counts as spoken once pos >= S - end (>= 0) */
+    int32_t skip;              /* 5: repetition looks at the columns [0, S - skip) (>= 0); texts of S <= skip ids are never suppressed */
+    float tail_thr, rep_thr;   /* 5.0, 5.0 (finite, >= 0) */
+    int32_t tok_rep;           /* 3: this many equal ids in a row force the stop; 0 = off (0..16) */
+} T3GuardParams;
+typedef struct { int32_t pos, complete, completed_at, forced_at, reason; float tail[3]; float rep; } T3GuardState;
+/* Non-NULL: allocates the per-slot state and control words and enables the guard with these parameters (again: replaces them).  NULL: frees
+ * them and disables it.  Valid only while nothing is queued or running (T3_E_STATE); a parameter out of range is T3_E_INVALID.  Drops the captured
+ * step graphs, as t3_set_alignment_heads does.  A request with alignment = 2 is T3_E_STATE while the guard is disabled and T3_E_INVALID with
+ * stop_token outside [0, 8194) or ignore_eos = 1.  With no such request in a step, the step launches what it launches with the guard disabled. */
+int t3_set_alignment_guard(T3Handle h, const T3GuardParams* params);
+/* The final guard state of a FINISHED, not yet released request submitted with alignment = 2.  Error codes as t3_get_alignment. */
+int t3_get_guard(T3Handle h, int64_t req_id, T3GuardState* out);
+
 /* ---- parity / measurement hooks --------------------------------------------------------- */
 /* post-CFG logits [8194] (speech-space, before the 2500-wide -inf pad of t3.py:669-672) of the
  * most recent sampled step of req_id; needs cfg.debug_logits = 1. */
@@ -296,6 +333,14 @@ int t3k_sample(const void* logits2_bf16, int32_t ldl, uint16_t* counts, const T3
 int t3k_sample_support(const void* logits2_bf16, int32_t ldl, uint16_t* counts, const T3Sampling* sp, float cfg,
                        uint32_t step, int32_t* token_out, uint8_t* keep_out_8194);
 int t3k_expf(const float* x, float* y, int32_t n);
+/* t3k_sample under a guard control word (0 nothing, 1 suppress sp->stop_token, 2 force it): the sampler's guarded instantiation. */
+int t3k_sample_ctl(const void* logits2_bf16, int32_t ldl, uint16_t* counts, const T3Sampling* sp, float cfg,
+                   uint32_t step, int32_t ctl, int32_t* token_out, float* logits_out_8194 /*nullable*/);
+/* The guard kernel (t3_guard.hip) over a host matrix A [n_frames][ld] (ld a multiple of 4, >= n_text; the columns from n_text on are never read
+ * into a result) and the ids tok [n_frames] drawn at each frame: one launch per frame in frame order, as the engine's steps do it.
+ * ctl_out [n_frames] = the control word of each frame, *final_state = the state behind the last one. */
+int t3k_alignment_guard(const float* A, int32_t n_frames, int32_t n_text, int32_t ld, const int32_t* tok, const T3GuardParams* params,
+                        int32_t* ctl_out, T3GuardState* final_state);
 /* ---- the FP8 (E4M3FN) KV pool, kv_cache_dtype = 1 ----
  * y = dequantised q8(x) on the device, q8(x) = e4m3fn(round-to-nearest-even(clamp(x, -448, 448))): the stored format of the FP8 pool. */
 int t3k_fp8_roundtrip(const float* x, float* y, int32_t n);
