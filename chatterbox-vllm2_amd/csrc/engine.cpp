@@ -61,6 +61,9 @@ struct Request {
     float* d_align = nullptr;         // finished, sp.alignment: its rows of the slot's alignment frames [out.size()][align_ld], a buffer of its own
     int align_ld = 0;                 // ... with the row pitch of the reserve it ran under
     bool has_guard = false;           // finished, sp.alignment == 2: the slot's guard state words sit in the last GUARD_STATE_WORDS floats of d_align
+    int lp_k = -1;                    // t3_request_logprobs: top ids kept per token (-1 = not marked)
+    int* d_lp = nullptr;              // finished, marked: its out.size() log-probability records of 2 (lp_K + 1) words, a pooled buffer of its own
+    int lp_K = 0;                     // ... with the maximum of the reserve it ran under
     double t_add = 0, t_admit = 0, t_first = 0, t_finish = 0;     // seconds since the engine was created (t3_get_timing)
 };
 
@@ -121,13 +124,14 @@ struct T3Engine {
         uint64_t waited_admit_seq = 0;     // the admission this group's stream has been ordered behind
         hipEvent_t ev_done[NBUF] = {};
         int rcap = 0;              // row budget per step
-        std::map<std::tuple<int, int, int, int, int>, hipGraphExec_t> graphs;   // (M, n_sel, first staging buffer, steps, tapped + 2 guarded) -> captured decode step(s)
+        std::map<std::tuple<int, int, int, int, int>, hipGraphExec_t> graphs;   // (M, n_sel, first staging buffer, steps, tapped + 2 guarded + 4 logprobs) -> captured decode step(s)
     };
     // One enqueued step: what the scheduler put on each group's stream, kept until its tokens are back.
     struct StepRec {
         int M = 0, n_sel = 0, n_prefill_rows = 0, decode_rows = 0;
         bool tapped = false;           // a sampled row of the step feeds the alignment export: the tap launches follow their layers' attention
         bool guarded = false;          // ... and one of them is guarded: the guard launch follows the last tap, the sampler obeys its control words
+        bool logprobs = false;         // a sampled request of the step is marked (t3_request_logprobs): the log-probability launch follows the sampler
         int max_prefill_ctx = 0;       // longest context among the step's prefill rows (sizes the tile attention's LDS)
         double sum_ctx = 0;
         std::vector<Request*> sampled;
@@ -170,6 +174,10 @@ struct T3Engine {
     // alignment guard (t3_set_alignment_guard, t3_guard.hip): per slot GUARD_STATE_WORDS state words and one control word; null = disabled
     int *d_guard_state = nullptr, *d_guard_ctl = nullptr;
     T3GuardParams guard{};
+    // per-token log-probabilities (t3_reserve_logprobs, t3_logprobs.hip): per slot [max_model_len steps][2 (lp_K + 1)] record words and one k word
+    // (-1 = the slot's request is not marked); lp_K < 0 = nothing reserved.  Finished requests keep their records in pooled buffers, as d_align does
+    int *d_lp_rec = nullptr, *d_lp_k = nullptr; int lp_K = -1;
+    std::vector<int*> lp_pool;         // free per-request record buffers of the current reserve (max_model_len x 2 (lp_K + 1) words each)
     std::deque<int64_t> finished_q;    // ids finished since the last t3_pop_finished (T3StepResult carries only the first 64 of a step)
     uint16_t* d_dbg_emb = nullptr;     // debug_logits: the embedded input rows of the most recent step (t3_debug_embeddings)
     std::vector<int> dbg_emb_rec;      // their (stream, position) pairs
@@ -280,7 +288,9 @@ extern "C" int t3_destroy(T3Handle e) {
     free_dev(e->d_handoff_items); free_dev(e->d_dbg_emb);
     free_dev(e->d_align); free_dev(e->d_guard_state); free_dev(e->d_guard_ctl);
     for (float* b : e->align_pool) free_dev(b);
-    for (auto& kv : e->reqs) free_dev(kv.second.d_align);
+    free_dev(e->d_lp_rec); free_dev(e->d_lp_k);
+    for (int* b : e->lp_pool) free_dev(b);
+    for (auto& kv : e->reqs) { free_dev(kv.second.d_align); free_dev(kv.second.d_lp); }
     if (e->ev_handoff) (void)hipEventDestroy(e->ev_handoff);
     if (e->ev_admit) (void)hipEventDestroy(e->ev_admit);
     for (int k = 0; k < K_COUNT; ++k) for (auto& p : e->pev[k]) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
@@ -542,6 +552,13 @@ static void release_align(T3Engine* e, Request& r) {
     else { (void)hipSetDevice(e->cfg.device_id); (void)hipFree(r.d_align); }
     r.d_align = nullptr;
 }
+// the same for its log-probability records
+static void release_lp(T3Engine* e, Request& r) {
+    if (!r.d_lp) return;
+    if (e->d_lp_rec && r.lp_K == e->lp_K) e->lp_pool.push_back(r.d_lp);
+    else { (void)hipSetDevice(e->cfg.device_id); (void)hipFree(r.d_lp); }
+    r.d_lp = nullptr;
+}
 // The captured decode steps bake in what the tap launches were given (the frame buffer, its pitch, the heads and which layers carry a tap):
 // whatever changes one of those drops them.  The caller has made sure nothing is queued or running.
 static int drop_graphs(T3Engine* e) {
@@ -587,6 +604,8 @@ static int admit(T3Engine* e) {
             HIP_TRY(launch_alignment_clear(e->d_align + (size_t)slot * e->cfg.max_model_len * e->align_ld, (size_t)r.limit * e->align_ld, e->groups[slot % e->n_groups].stream));
         // the guard's state and control word of the slot, on the same stream for the same reason (the previous occupant's state is copied out there)
         if (r.sp.alignment == 2) HIP_TRY(launch_guard_reset(e->d_guard_state, e->d_guard_ctl, slot, e->groups[slot % e->n_groups].stream));
+        // a marked request's k word, there too: the previous occupant's word went back to -1 on that stream when it finished
+        if (r.lp_k >= 0) HIP_TRY(launch_logprobs_mark(e->d_lp_k, slot, r.lp_k, e->groups[slot % e->n_groups].stream));
         // r.cond / r.sp are kept alive in the request map until the copy is consumed (stream-ordered, pageable -> staged synchronously)
         e->running.push_back(r.id);
     }
@@ -705,6 +724,10 @@ static int launch_sample_phase(T3Engine* e, T3Engine::Group& g, const T3Engine::
     { Prof p(e, K_SAMPLE, s); SampleArgs sa{g.logits, VPAD, g.dm.sel, e->d_counts, e->d_sp, e->cfg.cfg_scale, g.dm.out_tok, e->d_dbg, n_sel, e->d_hist, e->cfg.max_model_len, e->zero_copy ? g.h_out_tok[buf] : nullptr};
       if (sr.guarded) sa.eos_ctl = e->d_guard_ctl;
       HIP_TRY(launch_sampler(sa, s)); }
+    if (sr.logprobs) {     // outside Prof: not a kernel class of its own.  Reads what the sampler has just left in out_tok and the head rows it read
+        LogprobArgs la{g.logits, VPAD, g.dm.sel, g.dm.out_tok, e->d_lp_k, e->cfg.cfg_scale, e->d_lp_rec, e->cfg.max_model_len, e->lp_K, n_sel};
+        HIP_TRY(launch_logprobs(la, s));
+    }
     return T3_OK;
 }
 static int launch_step(T3Engine* e, T3Engine::Group& g, const T3Engine::StepRec& sr, int buf, hipStream_t s) {
@@ -768,7 +791,7 @@ static int build_step(T3Engine* e, T3Engine::Step& st, bool may_admit) {
         hm.sel[sr.n_sel] = make_int4(r.slot, n, 0, 0);
         sr.sum_ctx += 2.0 * (pos + 1);
         r.last_idx = sr.n_sel; r.n_sched = n + 1;
-        sr.sampled.push_back(&r); ++sr.n_sel;
+        sr.sampled.push_back(&r); ++sr.n_sel; sr.logprobs |= r.lp_k >= 0;
     }
     for (auto& sr : st.g) sr.decode_rows = sr.M;
     for (int64_t id : e->running) {
@@ -793,7 +816,7 @@ static int build_step(T3Engine* e, T3Engine::Step& st, bool may_admit) {
         if (p1 == T) {
             hm.sel[sr.n_sel] = make_int4(r.slot, 0, 0, 0);
             r.state = DECODE; r.n_sched = 1; r.last_idx = sr.n_sel;
-            sr.sampled.push_back(&r); ++sr.n_sel;
+            sr.sampled.push_back(&r); ++sr.n_sel; sr.logprobs |= r.lp_k >= 0;
         }
     }
     for (auto& sr : st.g) { st.M_all += sr.M; st.n_prefill_rows += sr.n_prefill_rows; st.n_sampled += sr.n_sel; st.decode_rows += sr.decode_rows; st.sum_ctx += sr.sum_ctx; }
@@ -837,7 +860,7 @@ static int launch_steps(T3Engine* e, T3Engine::Step* steps, int n) {
             for (int r = 0; r < sr.M; ++r) { const int* rec = g.hm[buf].rows + (size_t)r * e->row_stride; e->dbg_emb_rec[2 * r] = rec[0]; e->dbg_emb_rec[2 * r + 1] = rec[1]; }
         }
         if (graphs_ok) {
-            const auto key = std::make_tuple(sr.M, sr.n_sel, e->zero_copy ? buf : 0, n, (int)sr.tapped + 2 * (int)sr.guarded);      // zero-copy: the pinned buffers of `buf` ... are kernel arguments
+            const auto key = std::make_tuple(sr.M, sr.n_sel, e->zero_copy ? buf : 0, n, (int)sr.tapped + 2 * (int)sr.guarded + 4 * (int)sr.logprobs);      // zero-copy: the pinned buffers of `buf` ... are kernel arguments
             auto it = g.graphs.find(key);
             if (it == g.graphs.end()) {
                 hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
@@ -980,6 +1003,22 @@ static int complete_step(T3Engine* e, T3Engine::Step& st, T3StepResult* res, dou
                         }
                     }
                 }
+                if (r.lp_k >= 0) {
+                    // and for its log-probability records: records 0 .. n_tokens - 1 of the slot; then the slot's k word goes back to -1, behind the
+                    // steps already enqueued for it (they write records beyond n_tokens that nobody reads) and ahead of the next occupant's admission
+                    const size_t recw = (size_t)2 * (e->lp_K + 1), cap = (size_t)e->cfg.max_model_len * recw * 4;
+                    hipError_t ce = hipSuccess;
+                    if (!e->lp_pool.empty()) { r.d_lp = e->lp_pool.back(); e->lp_pool.pop_back(); }
+                    else ce = hipMalloc((void**)&r.d_lp, cap);
+                    if (ce != hipSuccess) { r.d_lp = nullptr; if (!dev_rc) dev_rc = e->fail(T3_E_NOMEM, "hipMalloc of " + std::to_string(cap) + " bytes for a finished request's log-probability records failed"); }
+                    else {
+                        r.lp_K = e->lp_K;
+                        ce = hipMemcpyAsync(r.d_lp, e->d_lp_rec + (size_t)r.slot * e->cfg.max_model_len * recw, r.out.size() * recw * 4, hipMemcpyDeviceToDevice, e->groups[gi].stream);
+                        if (ce != hipSuccess && !dev_rc) dev_rc = e->fail(T3_E_DEVICE, std::string("copy of a finished request's log-probability records failed: ") + hipGetErrorString(ce));
+                    }
+                    ce = launch_logprobs_mark(e->d_lp_k, r.slot, -1, e->groups[gi].stream);
+                    if (ce != hipSuccess && !dev_rc) dev_rc = e->fail(T3_E_DEVICE, std::string("clearing a finished slot's log-probability mark failed: ") + hipGetErrorString(ce));
+                }
                 if (res->n_finished < 64) res->finished_ids[res->n_finished] = r.id;
                 res->n_finished++;
                 e->finished_q.push_back(r.id);
@@ -1108,6 +1147,7 @@ extern "C" int t3_release_request(T3Handle e, int64_t req_id) {
     if (it->second.state != FINISHED) return e->fail(T3_E_STATE, "request still running");
     if (it->second.d_out) e->out_pool.push_back(it->second.d_out);
     release_align(e, it->second);
+    release_lp(e, it->second);
     e->reqs.erase(it);
     return T3_OK;
 }
@@ -1210,6 +1250,74 @@ extern "C" int t3_get_alignment(T3Handle e, int64_t req_id, float* out, int32_t*
     return T3_OK;
 }
 
+// ---- per-token log-probabilities ------------------------------------------------------------------------
+extern "C" int t3_reserve_logprobs(T3Handle e, int32_t max_k) {
+    if (!e) return T3_E_INVALID;
+    if (max_k > T3_MAX_LOGPROBS) return e->fail(T3_E_INVALID, "max_k beyond T3_MAX_LOGPROBS (20)");
+    if (!e->finalized) return e->fail(T3_E_STATE, "finalize_weights first");
+    if (!e->running.empty() || !e->waiting.empty()) return e->fail(T3_E_STATE, "t3_reserve_logprobs while requests are queued or running");
+    (void)hipSetDevice(e->cfg.device_id);
+    int rc;
+    if ((rc = drop_graphs(e))) return rc;      // they carry the launch, the record buffer and its record size
+    free_dev(e->d_lp_rec); free_dev(e->d_lp_k); e->d_lp_rec = nullptr; e->d_lp_k = nullptr; e->lp_K = -1;
+    for (int* b : e->lp_pool) free_dev(b);
+    e->lp_pool.clear();
+    if (max_k < 0) return T3_OK;
+    const size_t bytes = (size_t)e->cfg.max_seqs * e->cfg.max_model_len * 2 * (max_k + 1) * 4;
+    if (hipMalloc((void**)&e->d_lp_rec, bytes) != hipSuccess) {
+        e->d_lp_rec = nullptr;
+        return e->fail(T3_E_NOMEM, "hipMalloc of " + std::to_string(bytes) + " bytes for the log-probability records (max_seqs x max_model_len x 2 (max_k + 1) words) failed");
+    }
+    if (hipMalloc((void**)&e->d_lp_k, (size_t)e->cfg.max_seqs * 4) != hipSuccess) {
+        free_dev(e->d_lp_rec); e->d_lp_rec = nullptr; e->d_lp_k = nullptr;
+        return e->fail(T3_E_NOMEM, "hipMalloc of " + std::to_string((size_t)e->cfg.max_seqs * 4) + " bytes for the log-probability marks failed");
+    }
+    HIP_TRY(hipMemset(e->d_lp_k, 0xff, (size_t)e->cfg.max_seqs * 4));      // every slot: -1, not marked
+    e->lp_K = max_k;
+    return T3_OK;
+}
+
+extern "C" int t3_request_logprobs(T3Handle e, int64_t req_id, int32_t k) {
+    if (!e) return T3_E_INVALID;
+    auto it = e->reqs.find(req_id);
+    if (it == e->reqs.end()) return e->fail(T3_E_NOTFOUND, "unknown request id");
+    if (e->lp_K < 0) return e->fail(T3_E_STATE, "log-probabilities asked for before t3_reserve_logprobs");
+    if (it->second.state != WAITING) return e->fail(T3_E_STATE, "request " + std::to_string(req_id) + " is already admitted: mark it between t3_add_request and the next step");
+    if (k < 0 || k > e->lp_K) return e->fail(T3_E_INVALID, "k = " + std::to_string(k) + " outside [0, " + std::to_string(e->lp_K) + "], the reserved maximum");
+    it->second.lp_k = k;
+    return T3_OK;
+}
+
+extern "C" int t3_get_logprobs(T3Handle e, int64_t req_id, float* lp_tok, int32_t* rank, int32_t* top_ids, float* top_lp, int32_t* n_tokens, int32_t* k) {
+    if (!e || !n_tokens || !k) return T3_E_INVALID;
+    auto it = e->reqs.find(req_id);
+    if (it == e->reqs.end()) return e->fail(T3_E_NOTFOUND, "unknown request id");
+    const Request& r = it->second;
+    if (r.lp_k < 0) return e->fail(T3_E_INVALID, "request " + std::to_string(req_id) + " was not marked with t3_request_logprobs");
+    if (r.state != FINISHED) return e->fail(T3_E_STATE, "request " + std::to_string(req_id) + " has not finished");
+    const int n = (int)r.out.size(), cap = *n_tokens;
+    *n_tokens = n; *k = r.lp_k;
+    if (!lp_tok && !rank && !top_ids && !top_lp) return T3_OK;
+    if (cap < n) return e->fail(T3_E_INVALID, "log-probability buffers too small: " + std::to_string(n) + " tokens needed");
+    if (n == 0) return T3_OK;
+    if (!r.d_lp) return e->fail(T3_E_DEVICE, "the log-probability records of request " + std::to_string(req_id) + " could not be kept");
+    (void)hipSetDevice(e->cfg.device_id);
+    for (auto& g : e->groups) if (g.stream) HIP_TRY(hipStreamSynchronize(g.stream));      // the copy-out was queued on a group stream
+    const size_t recw = (size_t)2 * (r.lp_K + 1);
+    std::vector<int32_t> rec((size_t)n * recw);
+    HIP_TRY(hipMemcpy(rec.data(), r.d_lp, rec.size() * 4, hipMemcpyDeviceToHost));
+    for (int t = 0; t < n; ++t) {
+        const int32_t* w = rec.data() + (size_t)t * recw;
+        if (rank) rank[t] = w[0];
+        if (lp_tok) memcpy(lp_tok + t, w + 1, 4);
+        for (int i = 0; i < r.lp_k; ++i) {
+            if (top_ids) top_ids[(size_t)t * r.lp_k + i] = w[2 + 2 * i] + T3_SPEECH_TOKEN_OFFSET;
+            if (top_lp) memcpy(top_lp + (size_t)t * r.lp_k + i, w + 3 + 2 * i, 4);
+        }
+    }
+    return T3_OK;
+}
+
 // ---- alignment guard ---------------------------------------------------------------------------------
 extern "C" int t3_set_alignment_guard(T3Handle e, const T3GuardParams* params) {
     if (!e) return T3_E_INVALID;
@@ -1286,10 +1394,12 @@ extern "C" int t3_abort_request(T3Handle e, int64_t req_id) {
         (void)hipSetDevice(e->cfg.device_id);
         for (auto& g : e->groups) if (g.stream) (void)hipStreamSynchronize(g.stream);      // nothing of it may still be running
         e->running.erase(std::remove(e->running.begin(), e->running.end(), req_id), e->running.end());
+        if (r.lp_k >= 0 && r.slot >= 0 && e->d_lp_k) (void)launch_logprobs_mark(e->d_lp_k, r.slot, -1, e->groups[r.slot % e->n_groups].stream);
         release_slot(e, r);
     }
     if (r.d_out) e->out_pool.push_back(r.d_out);
     release_align(e, r);
+    release_lp(e, r);
     e->reqs.erase(it);
     return T3_OK;
 }

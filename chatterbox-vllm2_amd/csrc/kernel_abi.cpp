@@ -366,6 +366,26 @@ static int sample_impl(const void* logits2, int32_t ldl, uint16_t* counts, const
     return T3_OK;
 }
 
+/* the log-probability kernel for one utterance: slot 0, step 0, its own k as the reserved maximum, the token as the sampler's output word */
+extern "C" int t3k_logprobs(const void* logits2, int32_t ldl, float cfg, int32_t token, int32_t k, int32_t* rank, float* lp_tok,
+                            int32_t* top_ids, float* top_lp) {
+    if (!logits2 || !rank || !lp_tok || ldl < V || (ldl & 7) || token < 0 || token >= V || k < 0 || k > T3_MAX_LOGPROBS || (k > 0 && (!top_ids || !top_lp)))
+        return T3_E_INVALID;
+    if (!have_device()) return T3_E_DEVICE;
+    const int4 sel = make_int4(0, 0, 0, 0);
+    std::vector<int32_t> rec((size_t)2 * (k + 1), 0);
+    DevBuf dl, dsel, dtok, dk, drec;
+    K_TRY(dl.from(logits2, (size_t)2 * ldl * 2)); K_TRY(dsel.from(&sel, sizeof(sel))); K_TRY(dtok.from(&token, 4)); K_TRY(dk.from(&k, 4));
+    K_TRY(drec.alloc(rec.size() * 4, true));
+    LogprobArgs la{dl.as<uint16_t>(), ldl, dsel.as<int4>(), dtok.as<int>(), dk.as<int>(), cfg, drec.as<int>(), 1, k, 1};
+    K_TRY(launch_logprobs(la, nullptr));
+    K_TRY(hipDeviceSynchronize());
+    K_TRY(hipMemcpy(rec.data(), drec.p, rec.size() * 4, hipMemcpyDeviceToHost));
+    *rank = rec[0]; memcpy(lp_tok, &rec[1], 4);
+    for (int i = 0; i < k; ++i) { top_ids[i] = rec[2 + 2 * i]; memcpy(top_lp + i, &rec[3 + 2 * i], 4); }
+    return T3_OK;
+}
+
 /* the hand-off kernel on host buffers: ids [n] speech-space -> out [ld] (padded with 0), *len */
 extern "C" int t3k_handoff(const int32_t* ids, int32_t n, int32_t text_token_count, int32_t flags, int32_t* out, int32_t ld, int32_t* len) {
     if ((!ids && n > 0) || !out || !len || n < 0 || ld <= 0) return T3_E_INVALID;

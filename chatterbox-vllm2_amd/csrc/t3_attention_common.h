@@ -67,6 +67,19 @@ __device__ __forceinline__ float wave_max_f32(float m, int lane) {
     m = fmaxf(m, lane_xor<4>(m, lane)); m = fmaxf(m, lane_xor<2>(m, lane)); m = fmaxf(m, lane_xor<1>(m, lane));
     return m;
 }
+template <int OFF>
+__device__ __forceinline__ uint32_t lane_xor_u32(uint32_t v, int lane) { return __float_as_uint(lane_xor<OFF>(__uint_as_float(v), lane)); }
+// max over the wave of a u64 key (hi, lo), in every lane: the butterfly of wave_max_f32 on both halves (t3_guard.hip, t3_logprobs.hip)
+template <int OFF>
+__device__ __forceinline__ void key_max_step(uint32_t& hi, uint32_t& lo, int lane) {
+    const uint32_t ohi = lane_xor_u32<OFF>(hi, lane), olo = lane_xor_u32<OFF>(lo, lane);
+    const bool take = ohi > hi || (ohi == hi && olo > lo);
+    hi = take ? ohi : hi; lo = take ? olo : lo;
+}
+__device__ __forceinline__ void wave_max_key(uint32_t& hi, uint32_t& lo, int lane) {
+    key_max_step<32>(hi, lo, lane); key_max_step<16>(hi, lo, lane); key_max_step<8>(hi, lo, lane);
+    key_max_step<4>(hi, lo, lane); key_max_step<2>(hi, lo, lane); key_max_step<1>(hi, lo, lane);
+}
 __device__ __forceinline__ float wave_bfly_add_f32(float v, int lane) {      // contract order: xor 32, 16, 8, 4, 2, 1
     v = v + lane_xor<32>(v, lane); v = v + lane_xor<16>(v, lane); v = v + lane_xor<8>(v, lane);
     v = v + lane_xor<4>(v, lane); v = v + lane_xor<2>(v, lane); v = v + lane_xor<1>(v, lane);

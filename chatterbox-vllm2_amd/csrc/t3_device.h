@@ -44,6 +44,15 @@ __device__ __forceinline__ uint32_t f2bf(float f) {
 __device__ __forceinline__ float rbf(float f) { return __uint_as_float(f2bf(f) << 16); }
 __device__ __forceinline__ uint32_t pack2(float lo, float hi) { return f2bf(lo) | (f2bf(hi) << 16); }
 
+// The post-CFG logit of one id from the two head rows' bf16 values (t3.py:662: cond + cfg * (cond - uncond) in bf16 tensor arithmetic, one
+// rounding per operation).  One copy: the sampler's phase A and the log-probability kernel (t3_logprobs.hip) must see the same number.
+__device__ __forceinline__ float cfg_logit(uint16_t cond, uint16_t uncond, float cfg) {
+    const float c = bf2f(cond), un = bf2f(uncond);
+    const float d = rbf(c - un);
+    const float e = rbf(cfg * d);
+    return rbf(c + e);
+}
+
 // element j (0..7) of a 16-byte vector of 8 bf16, as fp32
 template <int J>
 __device__ __forceinline__ float elem(const uint4& v) {

@@ -40,20 +40,6 @@
 
 namespace t3 {
 
-template <int OFF>
-__device__ __forceinline__ uint32_t lane_xor_u32(uint32_t v, int lane) { return __float_as_uint(lane_xor<OFF>(__uint_as_float(v), lane)); }
-// max over the wave of a u64 key (hi, lo), in every lane: the butterfly of wave_max_f32 on both halves
-template <int OFF>
-__device__ __forceinline__ void key_max_step(uint32_t& hi, uint32_t& lo, int lane) {
-    const uint32_t ohi = lane_xor_u32<OFF>(hi, lane), olo = lane_xor_u32<OFF>(lo, lane);
-    const bool take = ohi > hi || (ohi == hi && olo > lo);
-    hi = take ? ohi : hi; lo = take ? olo : lo;
-}
-__device__ __forceinline__ void wave_max_key(uint32_t& hi, uint32_t& lo, int lane) {
-    key_max_step<32>(hi, lo, lane); key_max_step<16>(hi, lo, lane); key_max_step<8>(hi, lo, lane);
-    key_max_step<4>(hi, lo, lane); key_max_step<2>(hi, lo, lane); key_max_step<1>(hi, lo, lane);
-}
-
 __global__ __launch_bounds__(256) void guard_kernel(GuardArgs a) {
     const int lane = threadIdx.x & 63;
     const int u = (int)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);

@@ -187,6 +187,21 @@ struct GuardArgs {
 hipError_t launch_guard(const GuardArgs& a, hipStream_t s);
 hipError_t launch_guard_reset(int* state, int* ctl, int slot, hipStream_t s);   // the slot's state and control word = 0, by a kernel
 void guard_unpack_state(const int* words, T3GuardState* out);                  // host: state words -> the ABI's struct
+// Per-token log-probabilities (t3_logprobs.hip): workgroup u serves sampled utterance u directly behind the step's sampler -- the raw log-probability
+// and rank of the id it drew and the k = lp_k[slot] most likely ids, over the post-CFG logits of the 8194 speech ids.  Destination: the record
+// rec[(slot * rec_steps + step) * 2 (K + 1)] = {rank, lp_tok, (id, lp) x k}.  A workgroup whose slot is not marked (lp_k[slot] < 0) leaves at once.
+struct LogprobArgs {
+    const uint16_t* logits; int ldl;   // SampleArgs.logits / ldl (ldl a multiple of 8)
+    const int4* sel;           // per sampled utterance {slot, step, 0, 0}
+    const int* out_tok;        // [n]: what the sampler has just drawn
+    const int* lp_k;           // [max_seqs]: -1 = not marked, else k in 0 .. K
+    float cfg;
+    int* rec;                  // [max_seqs][rec_steps][2 (K + 1)] 32-bit words
+    int rec_steps, K;
+    int n;
+};
+hipError_t launch_logprobs(const LogprobArgs& a, hipStream_t s);
+hipError_t launch_logprobs_mark(int* lp_k, int slot, int k, hipStream_t s);     // lp_k[slot] = k, by a kernel
 // Profile mode: the next single-kernel launch of this thread (decode GEMM forms, fused / per-row attention, embed, sampler) takes these as
 // its start / stop events (hipExtLaunchKernelGGL); launch_events_armed() afterwards tells whether a launcher consumed them.
 void arm_launch_events(hipEvent_t start, hipEvent_t stop);

@@ -274,10 +274,7 @@ __global__ __launch_bounds__(STH) void sampler_kernel(SampleArgs a) {
     auto element = [&](uint16_t cb, uint16_t ub, uint32_t cnt, int v) -> float {
         float x = -INFINITY;
         if (v < V) {
-            const float c = bf2f(cb), un = bf2f(ub);
-            const float d = rbf(c - un);
-            const float e = rbf(a.cfg * d);
-            x = rbf(c + e);
+            x = cfg_logit(cb, ub, a.cfg);
             if constexpr (CTL) { if (v == suppress) x = -INFINITY; }
             if (a.dbg) a.dbg[(size_t)slot * V + v] = x;
             if (cnt > 0) {

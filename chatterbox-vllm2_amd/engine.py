@@ -101,6 +101,7 @@ ABI_SYMBOLS = [
     "t3k_fp8_roundtrip", "t3k_rope_attention_fp8", "t3k_decode_attention_fp8",
     "t3_reserve_alignment", "t3_set_alignment_heads", "t3_get_alignment", "t3k_attention_probs",
     "t3_set_alignment_guard", "t3_get_guard", "t3k_alignment_guard", "t3k_sample_ctl",
+    "t3_reserve_logprobs", "t3_request_logprobs", "t3_get_logprobs", "t3k_logprobs",
     "t3_cond_create", "t3_cond_destroy", "t3_cond_last_error", "t3_cond_load_tensor", "t3_cond_encode", "t3_cond_emotion_row",
     "t3k_ce_layernorm", "t3k_ce_linear", "t3k_ce_attention", "t3k_set_prefill_rows", "t3k_set_prefill_wide_rows",
 ]
@@ -178,6 +179,10 @@ def load_library():
     L.t3_get_guard.argtypes = [vp, i64, ct.POINTER(T3GuardState)]
     L.t3k_alignment_guard.argtypes = [vp, i32, i32, i32, vp, ct.POINTER(T3GuardParams), vp, ct.POINTER(T3GuardState)]
     L.t3k_sample_ctl.argtypes = [vp, i32, vp, ct.POINTER(T3Sampling), ct.c_float, ct.c_uint32, i32, vp, vp]
+    L.t3_reserve_logprobs.argtypes = [vp, i32]
+    L.t3_request_logprobs.argtypes = [vp, i64, i32]
+    L.t3_get_logprobs.argtypes = [vp, i64, vp, vp, vp, vp, ct.POINTER(i32), ct.POINTER(i32)]
+    L.t3k_logprobs.argtypes = [vp, i32, ct.c_float, i32, i32, ct.POINTER(i32), ct.POINTER(ct.c_float), vp, vp]
     L.t3_cond_create.argtypes = [i32, ct.POINTER(vp)]
     L.t3_cond_destroy.argtypes = [vp]
     L.t3_cond_last_error.restype = ct.c_char_p; L.t3_cond_last_error.argtypes = [vp]
@@ -248,6 +253,7 @@ class T3Engine:
                                   int(enforce_eager), int(debug_logits), int(n_groups), kv_code)
         self.alignment_max_text = 0       # text ids the alignment frames are reserved for (reserve_alignment)
         self.guard_params = None          # the enabled guard's parameters as a dict (set_alignment_guard), None = disabled
+        self.logprobs_max_k = -1          # top ids per token the log-probability records are reserved for (reserve_logprobs), -1 = none
         self.h = ct.c_void_p()
         rc = self.lib.t3_create(ct.byref(self.cfg), ct.byref(self.h))
         if rc:
@@ -389,6 +395,28 @@ class T3Engine:
         st = T3GuardState()
         self._chk(self.lib.t3_get_guard(self.h, int(req_id), ct.byref(st)))
         return guard_state_dict(st)
+
+    def reserve_logprobs(self, max_k: int):
+        """Allocate (max_k in 0..20) or, with a negative value, free the per-slot log-probability records: max_seqs x max_model_len x 2 (max_k + 1)
+        words.  Only while nothing is queued or running."""
+        self.logprobs_max_k = -1          # a reserve that fails leaves no buffer behind
+        self._chk(self.lib.t3_reserve_logprobs(self.h, int(max_k)))
+        self.logprobs_max_k = max(-1, int(max_k))
+
+    def request_logprobs(self, req_id: int, k: int):
+        """Mark a request that is still waiting (after add_request, before the next step): keep the raw log-probability and rank of every id it
+        draws and its k most likely ids (csrc/t3_logprobs.hip)."""
+        self._chk(self.lib.t3_request_logprobs(self.h, int(req_id), int(k)))
+
+    def get_logprobs(self, req_id: int):
+        """(lp_tok float32 [n], rank int32 [n], top_ids int32 [n, k] offset-space, top_lp float32 [n, k]) of a finished, unreleased, marked request."""
+        n = ct.c_int32(0); k = ct.c_int32(0)
+        self._chk(self.lib.t3_get_logprobs(self.h, int(req_id), None, None, None, None, ct.byref(n), ct.byref(k)))
+        lp = np.zeros(n.value, dtype=np.float32); rank = np.zeros(n.value, dtype=np.int32)
+        ids = np.zeros((n.value, k.value), dtype=np.int32); tlp = np.zeros((n.value, k.value), dtype=np.float32)
+        self._chk(self.lib.t3_get_logprobs(self.h, int(req_id), ct.c_void_p(lp.ctypes.data), ct.c_void_p(rank.ctypes.data), ct.c_void_p(ids.ctypes.data),
+                                           ct.c_void_p(tlp.ctypes.data), ct.byref(n), ct.byref(k)))
+        return lp, rank, ids, tlp
 
     def pop_finished(self, cap: int = 4096) -> List[int]:
         """ids of the requests that finished since the last call, oldest first"""
@@ -567,6 +595,17 @@ def k_sample_ctl(logits2: torch.Tensor, counts: torch.Tensor, sp: T3Sampling, cf
     _chk_k(load_library().t3k_sample_ctl(logits2.data_ptr(), logits2.shape[1], counts.data_ptr(), ct.byref(sp), ct.c_float(cfg),
                                          ct.c_uint32(step), int(ctl), ct.byref(tok), None), "t3k_sample_ctl")
     return int(tok.value)
+
+
+def k_logprobs(logits2: torch.Tensor, cfg: float, token: int, k: int):
+    """The log-probability kernel on logits2 [2, ld] bf16 (cond, uncond) for the drawn speech-space id `token`
+    -> (rank, lp_tok, top_ids int32 [k] speech-space, top_lp float32 [k])."""
+    logits2 = _bf(logits2)
+    rank = ct.c_int32(0); lp = ct.c_float(0)
+    ids = np.zeros(max(1, k), dtype=np.int32); tlp = np.zeros(max(1, k), dtype=np.float32)
+    _chk_k(load_library().t3k_logprobs(logits2.data_ptr(), logits2.shape[1], ct.c_float(cfg), int(token), int(k), ct.byref(rank), ct.byref(lp),
+                                       ids.ctypes.data, tlp.ctypes.data), "t3k_logprobs")
+    return int(rank.value), float(lp.value), ids[:k], tlp[:k]
 
 
 def k_fp8_roundtrip(x: torch.Tensor) -> torch.Tensor:

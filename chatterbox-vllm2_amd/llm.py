@@ -25,11 +25,22 @@ from .prompt import TextTokenizer, assemble_prompt_ids, find_tokenizer_file
 from .weights import iter_safetensors, synthetic_tensors
 
 
+MAX_LOGPROBS = 20      # vLLM's default max_logprobs; T3_MAX_LOGPROBS of include/t3_engine.h
+
+
+@dataclass
+class Logprob:
+    """vLLM's Logprob: the raw log-probability of an id, its rank among the 8194 speech ids (1 = most likely; ties count for the drawn id)."""
+    logprob: float
+    rank: Optional[int] = None
+    decoded_token: Optional[str] = None
+
+
 class SamplingParams:
     """The subset of vllm.SamplingParams that reaches the sampler on this path (tts.py:455-464),
     with vLLM's names and defaults.  Unknown keyword arguments are rejected like vLLM does."""
 
-    _IGNORED = {"logprobs", "prompt_logprobs", "detokenize", "skip_special_tokens", "spaces_between_special_tokens",
+    _IGNORED = {"prompt_logprobs", "detokenize", "skip_special_tokens", "spaces_between_special_tokens",
                 "include_stop_str_in_output", "output_kind", "stop", "bad_words", "logit_bias", "allowed_token_ids",
                 "truncate_prompt_tokens", "guided_decoding", "extra_args", "min_tokens", "best_of", "logits_processors"}
 
@@ -37,7 +48,7 @@ class SamplingParams:
                  repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
                  seed: Optional[int] = None, stop_token_ids: Optional[List[int]] = None, max_tokens: Optional[int] = 16,
                  ignore_eos: bool = False, pos_policy: int = 0, alignment: bool = False,
-                 alignment_guard: Union[bool, dict, None] = False, **kwargs):
+                 alignment_guard: Union[bool, dict, None] = False, logprobs: Optional[int] = None, **kwargs):
         for k, v in kwargs.items():
             if k not in self._IGNORED:
                 raise TypeError(f"SamplingParams got an unexpected keyword argument {k!r}")
@@ -61,6 +72,13 @@ class SamplingParams:
         self.repetition_penalty, self.presence_penalty, self.frequency_penalty = repetition_penalty, presence_penalty, frequency_penalty
         self.seed, self.stop_token_ids, self.max_tokens, self.ignore_eos = seed, list(stop_token_ids or []), max_tokens, ignore_eos
         self.pos_policy = pos_policy
+        # vLLM's logprobs: None = off; k in 0..20 = the log-probability and rank of every drawn id plus the k most likely ids per token
+        # (CompletionOutput.logprobs / cumulative_logprob), from a kernel behind the sampler (csrc/t3_logprobs.hip).  Only vLLM's default mode is
+        # built: RAW log-probabilities of the post-CFG logits -- penalties, temperature, top-k / top-p / min-p and the alignment guard's suppression
+        # do not enter.  prompt_logprobs stays ignored and there is no logprobs_mode.
+        if logprobs is not None and not 0 <= int(logprobs) <= MAX_LOGPROBS:
+            raise ValueError(f"logprobs must be in [0, {MAX_LOGPROBS}], got {logprobs}")
+        self.logprobs = None if logprobs is None else int(logprobs)
         # extension: keep the text-speech alignment matrix of the request (CompletionOutput.alignment) -- what upstream's
         # AlignmentStreamAnalyzer reads from its attention hooks and a vLLM engine cannot hand out
         self.alignment = bool(alignment)
@@ -87,8 +105,8 @@ class CompletionOutput:
     index: int
     text: str
     token_ids: List[int]
-    cumulative_logprob: Optional[float] = None
-    logprobs: Optional[Any] = None
+    cumulative_logprob: Optional[float] = None    # SamplingParams(logprobs=k): the float64 sum of the drawn ids' raw log-probabilities, in token order
+    logprobs: Optional[List[Dict[int, Logprob]]] = None      # ... and per token {offset-space id: Logprob} for the drawn id and the k most likely ids
     finish_reason: Optional[str] = None
     stop_reason: Union[int, str, None] = None
     alignment: Optional[torch.Tensor] = None      # SamplingParams(alignment=True): CPU float32 [n_tokens, n_text], row k = frame k's attention over the text
@@ -242,16 +260,26 @@ class LLM:
             if keep_for_handoff and not kept_before:
                 self.engine.reserve_handoff(0)      # finished requests keep the buffers they hold; no new ones are made
         outs = []
-        for rid, text, final, tap, guarded in metas:
+        for rid, text, final, tap, guarded, want_lp in metas:
             toks, fr = self.engine.get_output(rid)
             align = self.engine.get_alignment(rid) if tap else None
             guard = self.engine.get_guard(rid) if guarded else None
+            lps = cum = None
+            if want_lp:
+                lp, rank, ids, tlp = self.engine.get_logprobs(rid)
+                lps = []
+                for t, tok in enumerate(toks):
+                    d = {int(i): Logprob(float(v), n + 1) for n, (i, v) in enumerate(zip(ids[t], tlp[t]))}
+                    d[tok] = Logprob(float(lp[t]), int(rank[t]))
+                    lps.append(d)
+                cum = float(lp.astype("float64").sum())
             if not keep_for_handoff:
                 self.engine.release(rid)
             reason = {1: "stop", 2: "length"}.get(fr)
             outs.append(RequestOutput(request_id=str(rid), prompt=text, prompt_token_ids=final,
                                       outputs=[CompletionOutput(index=0, text="", token_ids=toks, finish_reason=reason,
-                                                                stop_reason=(toks[-1] if fr == 1 else None), alignment=align, guard=guard)]))
+                                                                stop_reason=(toks[-1] if fr == 1 else None), alignment=align, guard=guard,
+                                                                logprobs=lps, cumulative_logprob=cum)]))
         return outs
 
     def handoff_tokens(self, outputs: Sequence[RequestOutput], text_token_counts: Sequence[int], range_filter: bool = True):
@@ -282,6 +310,9 @@ class LLM:
                 self.engine.set_alignment_guard(guards[0])       # the first guarded call enables the guard with its parameters
             elif any(self.engine.guard_params[k] != getattr(make_guard_params(guards[0]), k) for k in guards[0]):      # as the C struct rounds them
                 raise ValueError(f"alignment_guard {guards[0]} differs from the engine's enabled guard {self.engine.guard_params}")
+        asked = [sp.logprobs for sp in sps if sp.logprobs is not None]
+        if asked and max(asked) > self.engine.logprobs_max_k:
+            self.engine.reserve_logprobs(max(asked))         # once for the call's largest k, before anything of it is queued
         for i, ((text, tids, cond), sp) in enumerate(zip(texts, sps)):
             final = assemble_prompt_ids(tids)
             stop = -1
@@ -304,7 +335,9 @@ class LLM:
             rid = self._next_id; self._next_id += 1
             self.engine.add_request(rid, final, cond, esp)
             queued.append(rid)
-            metas.append((rid, text, final, sp.alignment, sp.alignment_guard is not None))
+            if sp.logprobs is not None:
+                self.engine.request_logprobs(rid, sp.logprobs)
+            metas.append((rid, text, final, sp.alignment, sp.alignment_guard is not None, sp.logprobs is not None))
 
     def shutdown(self):
         self.engine.close()

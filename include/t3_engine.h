@@ -237,6 +237,31 @@ int t3_set_alignment_guard(T3Handle h, const T3GuardParams* params);
 /* The final guard state of a FINISHED, not yet released request submitted with alignment = 2.  Error codes as t3_get_alignment. */
 int t3_get_guard(T3Handle h, int64_t req_id, T3GuardState* out);
 
+/* ---- per-token log-probabilities -----------------------------------------------------------------------------------------
+ * vLLM's SamplingParams(logprobs=k), from a kernel directly behind the sampler (t3_logprobs.hip): the post-CFG logits live on the device for one
+ * step only, so nothing outside the engine can compute these.  For a marked request and every token it draws, over the 8194 speech ids v:
+ *   x_v    = the post-CFG logit as the sampler forms it, BEFORE penalties, temperature, min-p / top-k / top-p and the guard's suppression (what
+ *            t3_debug_logits reports): vLLM's default "raw" log-probabilities.  A guard-forced stop id reports its raw value like any other id;
+ *   lp_v   = (x_v - M) - logf(Z),  M = max_v x_v,  Z = sum_v exp(x_v - M) in fp32 in one fixed order;
+ *   rank   = #{v : x_v >= x_tok}  (vLLM's definition: ties count);
+ *   top[i] = the ids ordered by (x_v descending, v ascending), i < k, decided on the exact fp32 logits.
+ * The numbers of a request are bit-identical between eager steps, captured graphs, bursts and batch compositions; token ids never depend on the
+ * feature, bursts and run-ahead stay on, and a step that samples no marked request launches exactly what it launches without it.
+ * t3_reserve_logprobs: max_k in 0..T3_MAX_LOGPROBS allocates the per-slot records, max_seqs x max_model_len x 2 (max_k + 1) 32-bit words, and the
+ * per-slot k words; max_k < 0 frees them; max_k > T3_MAX_LOGPROBS is T3_E_INVALID; T3_E_NOMEM names the byte count.  Valid only while nothing is
+ * queued or running (T3_E_STATE).  Drops the captured step graphs, as t3_reserve_alignment does.  The records of finished requests live in pooled
+ * buffers that t3_release_request gives back for reuse. */
+#define T3_MAX_LOGPROBS 20          /* vLLM's default max_logprobs */
+int t3_reserve_logprobs(T3Handle h, int32_t max_k);
+/* Marks a request that is still waiting (between t3_add_request and the next step call): k = 0 keeps the drawn id's log-probability and rank
+ * only.  Unknown id: T3_E_NOTFOUND; before a reserve, or once the request is admitted: T3_E_STATE; k outside [0, max_k]: T3_E_INVALID. */
+int t3_request_logprobs(T3Handle h, int64_t req_id, int32_t k);
+/* The numbers of a FINISHED, not yet released, marked request.  On entry *n_tokens is the capacity of every array in tokens; on exit *n_tokens (the
+ * number of tokens t3_get_output returns) and *k hold the real extents.  lp_tok / rank [n_tokens]; top_ids / top_lp row-major [n_tokens][k],
+ * top_ids in OFFSET space (speech id + 2500) like t3_get_output.  All four arrays may be NULL to ask for the extents only (each may be NULL on its
+ * own).  Error codes as t3_get_alignment. */
+int t3_get_logprobs(T3Handle h, int64_t req_id, float* lp_tok, int32_t* rank, int32_t* top_ids, float* top_lp, int32_t* n_tokens, int32_t* k);
+
 /* ---- parity / measurement hooks --------------------------------------------------------- */
 /* post-CFG logits [8194] (speech-space, before the 2500-wide -inf pad of t3.py:669-672) of the
  * most recent sampled step of req_id; needs cfg.debug_logits = 1. */
@@ -341,6 +366,10 @@ int t3k_sample_ctl(const void* logits2_bf16, int32_t ldl, uint16_t* counts, cons
  * ctl_out [n_frames] = the control word of each frame, *final_state = the state behind the last one. */
 int t3k_alignment_guard(const float* A, int32_t n_frames, int32_t n_text, int32_t ld, const int32_t* tok, const T3GuardParams* params,
                         int32_t* ctl_out, T3GuardState* final_state);
+/* The log-probability kernel (t3_logprobs.hip) for one utterance on host buffers: logits bf16 [2][ldl] as t3k_sample takes them (ldl a multiple of
+ * 8), token = the drawn speech-space id, k in 0..T3_MAX_LOGPROBS.  top_ids (SPEECH-space) / top_lp [k], nullable when k = 0. */
+int t3k_logprobs(const void* logits2_bf16, int32_t ldl, float cfg, int32_t token, int32_t k, int32_t* rank, float* lp_tok,
+                 int32_t* top_ids, float* top_lp);
 /* ---- the FP8 (E4M3FN) KV pool, kv_cache_dtype = 1 ----
  * y = dequantised q8(x) on the device, q8(x) = e4m3fn(round-to-nearest-even(clamp(x, -448, 448))): the stored format of the FP8 pool. */
 int t3k_fp8_roundtrip(const float* x, float* y, int32_t n);
