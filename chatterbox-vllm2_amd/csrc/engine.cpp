@@ -99,8 +99,10 @@ struct T3Engine {
     int64_t weight_bytes = 0;
 
     // KV pool + tables
-    unsigned char* kv = nullptr;   // the paged pool: kv_esz bytes per element (2: bf16, 1: FP8 E4M3)
-    int kv_esz = 2;
+    unsigned char* kv = nullptr;   // the paged pool, sized in bytes per block: bf16 2 bytes per element, FP8 E4M3 1, MXFP4 half a byte and its scales
+    int kv_dtype = 0;              // cfg.kv_cache_dtype: 0 bf16, 1 FP8, 4 MXFP4
+    size_t kv_block_bytes = (size_t)KV_BLOCK_ELEMS * 2;   // per layer per block, padding included
+    int kv_token_bytes = 2 * H * HD * 2;                  // per layer per token, what a decode step streams: 4096 / 2048 / 1088
     std::vector<int> free_blocks;
     int* d_block_table = nullptr;
     std::vector<int> h_block_table;
@@ -219,7 +221,8 @@ extern "C" int t3_create(const T3EngineConfig* cfg, T3Handle* out) {
     if (cfg->max_model_len < T3_COND_ROWS + 2 || cfg->max_model_len > 8192) return fail_create(T3_E_INVALID, "max_model_len out of range [36, 8192]");
     if (cfg->max_seqs <= 0 || cfg->max_seqs > 4096) return fail_create(T3_E_INVALID, "max_seqs out of range");
     if (cfg->text_vocab <= 697) return fail_create(T3_E_INVALID, "text_vocab must cover the placeholder ids 695..697");
-    if (cfg->kv_cache_dtype != 0 && cfg->kv_cache_dtype != 1) return fail_create(T3_E_INVALID, "kv_cache_dtype must be 0 (bf16) or 1 (fp8 e4m3)");
+    if (cfg->kv_cache_dtype != 0 && cfg->kv_cache_dtype != 1 && cfg->kv_cache_dtype != 4)
+        return fail_create(T3_E_INVALID, "kv_cache_dtype must be 0 (bf16), 1 (fp8 e4m3) or 4 (mxfp4)");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail_create(T3_E_DEVICE, "no HIP device: this engine has no CPU fallback");
@@ -227,7 +230,9 @@ extern "C" int t3_create(const T3EngineConfig* cfg, T3Handle* out) {
     if (hipSetDevice(cfg->device_id) != hipSuccess) return fail_create(T3_E_DEVICE, "hipSetDevice failed");
     T3Engine* e = new T3Engine();
     e->cfg = *cfg;
-    e->kv_esz = cfg->kv_cache_dtype == 1 ? 1 : 2;
+    e->kv_dtype = cfg->kv_cache_dtype;
+    e->kv_block_bytes = e->kv_dtype == 4 ? (size_t)KV4_BLOCK_BYTES : (size_t)KV_BLOCK_ELEMS * (e->kv_dtype == 1 ? 1 : 2);
+    e->kv_token_bytes = e->kv_dtype == 4 ? 2 * H * (HD / 2 + 2) : 2 * H * HD * (e->kv_dtype == 1 ? 1 : 2);
     if (e->cfg.cfg_scale != e->cfg.cfg_scale) e->cfg.cfg_scale = 0.5f;
     e->layers.resize(cfg->n_layers);
     e->max_blocks = (cfg->max_model_len + KV_BLOCK - 1) / KV_BLOCK;
@@ -477,7 +482,7 @@ extern "C" int t3_finalize_weights(T3Handle e) {
     HIP_TRY(t3::prepare_kernels());
     // KV pool
     {
-        const size_t per_block = (size_t)e->cfg.n_layers * KV_BLOCK_ELEMS * e->kv_esz;   // bytes
+        const size_t per_block = (size_t)e->cfg.n_layers * e->kv_block_bytes;
         int64_t bytes = e->cfg.kv_bytes;
         const int64_t want_all = (int64_t)2 * S * e->max_blocks * per_block;       // every slot at full length
         if (bytes <= 0) {
@@ -491,7 +496,7 @@ extern "C" int t3_finalize_weights(T3Handle e) {
         e->n_blocks = bytes / (int64_t)per_block;
         if (e->n_blocks < 2 * e->max_blocks) return e->fail(T3_E_NOMEM, "KV pool too small for even one utterance at max_model_len");
         // layout [layer][block][kv][head][tok][64]
-        if ((rc = dalloc(e, &e->kv, (size_t)e->n_blocks * e->cfg.n_layers * KV_BLOCK_ELEMS * e->kv_esz, true))) return rc;
+        if ((rc = dalloc(e, &e->kv, (size_t)e->n_blocks * per_block, true))) return rc;
         e->free_blocks.resize(e->n_blocks);
         for (int64_t i = 0; i < e->n_blocks; ++i) e->free_blocks[i] = (int)(e->n_blocks - 1 - i);
     }
@@ -657,12 +662,15 @@ static int launch_qkv_phase(T3Engine* e, T3Engine::Group& g, const T3Engine::Ste
 }
 static int launch_attention_phase(T3Engine* e, T3Engine::Group& g, const T3Engine::StepRec& sr, int L, hipStream_t s) {
     const int M = sr.M;
-    const size_t layer_elems = (size_t)e->n_blocks * KV_BLOCK_ELEMS;
     const int max_chunks = (e->cfg.max_model_len + CHUNK - 1) / CHUNK;
-    uint16_t* kvL = reinterpret_cast<uint16_t*>(e->kv + (size_t)L * layer_elems * e->kv_esz);      // FP8 pool: one-byte elements behind the same argument structs
-    const bool fp8 = e->kv_esz == 1;
-    auto launch_attention = [fp8](const AttnArgs& a, hipStream_t st) { return fp8 ? t3::launch_attention_fp8(a, st) : t3::launch_attention(a, st); };
-    auto launch_rope_kv = [fp8](const RopeArgs& a, hipStream_t st) { return fp8 ? t3::launch_rope_kv_fp8(a, st) : t3::launch_rope_kv(a, st); };
+    uint16_t* kvL = reinterpret_cast<uint16_t*>(e->kv + (size_t)L * e->n_blocks * e->kv_block_bytes);      // FP8 / MXFP4 pool: bytes behind the same argument structs
+    const int fmt = e->kv_dtype;
+    auto launch_attention = [fmt](const AttnArgs& a, hipStream_t st) {
+        return fmt == 4 ? t3::launch_attention_fp4(a, st) : fmt == 1 ? t3::launch_attention_fp8(a, st) : t3::launch_attention(a, st);
+    };
+    auto launch_rope_kv = [fmt](const RopeArgs& a, hipStream_t st) {
+        return fmt == 4 ? t3::launch_rope_kv_fp4(a, st) : fmt == 1 ? t3::launch_rope_kv_fp8(a, st) : t3::launch_rope_kv(a, st);
+    };
     const int dec = sr.n_prefill_rows > 0 ? sr.decode_rows : M;      // decode rows come first in the step's row list
     if (e->fuse_rope) {
         // decode rows: every one is the newest position of its stream -> RoPE + KV write inside the attention kernel
@@ -687,9 +695,9 @@ static int launch_attention_phase(T3Engine* e, T3Engine::Group& g, const T3Engin
 static int launch_alignment_phase(T3Engine* e, T3Engine::Group& g, const T3Engine::StepRec& sr, int L, hipStream_t s) {
     for (int t = 0; t < e->n_taps; ++t) {
         if (e->taps[t][0] != L) continue;
-        AlignArgs a{g.qkv, e->kv + (size_t)L * e->n_blocks * KV_BLOCK_ELEMS * e->kv_esz, g.dm.rows, e->row_stride, g.dm.sel_rows, e->cos_t, e->sin_t, e->d_align,
+        AlignArgs a{g.qkv, e->kv + (size_t)L * e->n_blocks * e->kv_block_bytes, g.dm.rows, e->row_stride, g.dm.sel_rows, e->cos_t, e->sin_t, e->d_align,
                     sr.n_sel, e->taps[t][1], T3_COND_ROWS, (e->cfg.max_model_len + CHUNK - 1) / CHUNK, e->cfg.max_model_len, e->align_ld, t, e->n_taps, 1.0f / (float)e->n_taps};
-        HIP_TRY(launch_alignment(a, e->kv_esz == 1, s));
+        HIP_TRY(launch_alignment(a, e->kv_dtype, s));
     }
     return T3_OK;
 }
@@ -938,7 +946,7 @@ static int complete_step(T3Engine* e, T3Engine::Step& st, T3StepResult* res, dou
     if (decode_only) {
         e->st.decode_steps++; e->st.gpu_ms_decode += ms; e->st.sum_ctx_decode += st.sum_ctx;
         // W + KV read + KV write + embedding rows, scaled to n_layers
-        const double per_tok_stream = 2.0 * e->cfg.n_layers * H * HD * e->kv_esz;
+        const double per_tok_stream = (double)e->cfg.n_layers * e->kv_token_bytes;
         e->st.algo_bytes_decode += (double)e->weight_bytes_for_step() + per_tok_stream * st.sum_ctx + per_tok_stream * st.decode_rows + (st.decode_rows / 2) * 4096.0;
     }
     if (e->profile) {

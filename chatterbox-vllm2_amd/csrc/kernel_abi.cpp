@@ -28,6 +28,13 @@ struct DevBuf {
     template <typename T> T* as() { return reinterpret_cast<T*>(p); }
 };
 bool have_device() { int n = 0; return hipGetDeviceCount(&n) == hipSuccess && n > 0; }
+// the launchers and the pool bytes per block of a storage format (T3EngineConfig.kv_cache_dtype: 0 bf16, 1 FP8 E4M3, 4 MXFP4)
+size_t kv_block_bytes(int fmt) { return fmt == 4 ? (size_t)KV4_BLOCK_BYTES : (size_t)KV_BLOCK_ELEMS * (fmt == 1 ? 1 : 2); }
+hipError_t rope_kv_of(int fmt, const RopeArgs& a) { return fmt == 4 ? launch_rope_kv_fp4(a, nullptr) : fmt == 1 ? launch_rope_kv_fp8(a, nullptr) : launch_rope_kv(a, nullptr); }
+hipError_t attention_of(int fmt, const AttnArgs& a) { return fmt == 4 ? launch_attention_fp4(a, nullptr) : fmt == 1 ? launch_attention_fp8(a, nullptr) : launch_attention(a, nullptr); }
+hipError_t kv_gather_of(int fmt, const uint16_t* kv, const int* rec, int stride, int rows, uint16_t* out) {
+    return fmt == 4 ? launch_kv_gather_fp4(kv, rec, stride, rows, out, nullptr) : fmt == 1 ? launch_kv_gather_fp8(kv, rec, stride, rows, out, nullptr) : launch_kv_gather(kv, rec, stride, rows, out, nullptr);
+}
 }  // namespace
 
 #define K_TRY(expr) do { if ((expr) != hipSuccess) return T3_E_DEVICE; } while (0)
@@ -147,9 +154,9 @@ extern "C" int t3k_silu_mul_gemm(const void* h, const void* ln_w, const void* wg
     return T3_OK;
 }
 
-// fp8: the same call over an FP8 (E4M3) pool -- one-byte elements, the FP8 launchers; kv_out (nullable) [rows][2][1024] = the stored K / V read back
+// fmt 1 / 4: the same call over an FP8 (E4M3) / MXFP4 pool -- byte pools, their own launchers; kv_out (nullable) [rows][2][1024] = the stored K / V read back
 static int rope_attention_impl(const void* qkv, const int32_t* row_stream, const int32_t* row_pos, int32_t rows,
-                               int32_t n_streams, int32_t max_pos, void* out, bool fp8, void* kv_out) {
+                               int32_t n_streams, int32_t max_pos, void* out, int fmt, void* kv_out) {
     if (!qkv || !row_stream || !row_pos || !out || rows <= 0 || n_streams <= 0 || max_pos <= 0) return T3_E_INVALID;
     if (!have_device()) return T3_E_DEVICE;
     for (int r = 0; r < rows; ++r)
@@ -176,13 +183,13 @@ static int rope_attention_impl(const void* qkv, const int32_t* row_stream, const
     DevBuf dqkv, drec, dc, ds, dq, dkv, dout;
     K_TRY(dqkv.from(qkv, (size_t)rows * QKV * 2)); K_TRY(drec.from(recs.data(), recs.size() * 4));
     K_TRY(dc.from(c.data(), c.size() * 4)); K_TRY(ds.from(s.data(), s.size() * 4));
-    K_TRY(dq.alloc((size_t)rows * D * 2)); K_TRY(dkv.alloc((size_t)nb * KV_BLOCK_ELEMS * (fp8 ? 1 : 2), true)); K_TRY(dout.alloc((size_t)rows * D * 2, true));
+    K_TRY(dq.alloc((size_t)rows * D * 2)); K_TRY(dkv.alloc((size_t)nb * kv_block_bytes(fmt), true)); K_TRY(dout.alloc((size_t)rows * D * 2, true));
     RopeArgs ra{dqkv.as<uint16_t>(), dq.as<uint16_t>(), dkv.as<uint16_t>(), drec.as<int>(), stride, dc.as<float>(), ds.as<float>(), rows};
-    K_TRY(fp8 ? launch_rope_kv_fp8(ra, nullptr) : launch_rope_kv(ra, nullptr));
+    K_TRY(rope_kv_of(fmt, ra));
     AttnArgs aa{dq.as<uint16_t>(), dkv.as<uint16_t>(), drec.as<int>(), stride, dout.as<uint16_t>(), rows, (max_pos + CHUNK - 1) / CHUNK, nullptr, nullptr, nullptr, nullptr, 0, 0};     // every row through the 16-row tile schedule
-    K_TRY(fp8 ? launch_attention_fp8(aa, nullptr) : launch_attention(aa, nullptr));
+    K_TRY(attention_of(fmt, aa));
     DevBuf dkvo;
-    if (kv_out) { K_TRY(dkvo.alloc((size_t)rows * 2 * D * 2, true)); K_TRY(launch_kv_gather_fp8(dkv.as<uint16_t>(), drec.as<int>(), stride, rows, dkvo.as<uint16_t>(), nullptr)); }
+    if (kv_out) { K_TRY(dkvo.alloc((size_t)rows * 2 * D * 2, true)); K_TRY(kv_gather_of(fmt, dkv.as<uint16_t>(), drec.as<int>(), stride, rows, dkvo.as<uint16_t>())); }
     K_TRY(hipDeviceSynchronize());
     K_TRY(hipMemcpy(out, dout.p, (size_t)rows * D * 2, hipMemcpyDeviceToHost));
     if (kv_out) K_TRY(hipMemcpy(kv_out, dkvo.p, (size_t)rows * 2 * D * 2, hipMemcpyDeviceToHost));
@@ -190,11 +197,15 @@ static int rope_attention_impl(const void* qkv, const int32_t* row_stream, const
 }
 extern "C" int t3k_rope_attention(const void* qkv, const int32_t* row_stream, const int32_t* row_pos, int32_t rows,
                                   int32_t n_streams, int32_t max_pos, void* out) {
-    return rope_attention_impl(qkv, row_stream, row_pos, rows, n_streams, max_pos, out, false, nullptr);
+    return rope_attention_impl(qkv, row_stream, row_pos, rows, n_streams, max_pos, out, 0, nullptr);
 }
 extern "C" int t3k_rope_attention_fp8(const void* qkv, const int32_t* row_stream, const int32_t* row_pos, int32_t rows,
                                       int32_t n_streams, int32_t max_pos, void* out, void* kv_out) {
-    return rope_attention_impl(qkv, row_stream, row_pos, rows, n_streams, max_pos, out, true, kv_out);
+    return rope_attention_impl(qkv, row_stream, row_pos, rows, n_streams, max_pos, out, 1, kv_out);
+}
+extern "C" int t3k_rope_attention_fp4(const void* qkv, const int32_t* row_stream, const int32_t* row_pos, int32_t rows,
+                                      int32_t n_streams, int32_t max_pos, void* out, void* kv_out) {
+    return rope_attention_impl(qkv, row_stream, row_pos, rows, n_streams, max_pos, out, 4, kv_out);
 }
 
 /* The alignment tap (t3_alignment.hip): every row goes into a scrambled paged pool through the prefill path (rope_kv), then ONE tap launch serves every
@@ -202,11 +213,10 @@ extern "C" int t3k_rope_attention_fp8(const void* qkv, const int32_t* row_stream
 extern "C" int t3k_attention_probs(const void* qkv, const int32_t* row_stream, const int32_t* row_pos, int32_t rows, int32_t n_streams, int32_t max_pos,
                                    int32_t head, int32_t lo, int32_t hi, int32_t kv_dtype, float* out, void* q_rot, void* kv_out) {
     if (!qkv || !row_stream || !row_pos || !out || rows <= 0 || n_streams <= 0 || max_pos <= 0 || head < 0 || head >= H || lo < 0 || hi <= lo || hi > max_pos ||
-        (kv_dtype != 0 && kv_dtype != 1) || max_pos > 8192 /* the engine's own limit; the tap's LDS strip grows with it */) return T3_E_INVALID;
+        (kv_dtype != 0 && kv_dtype != 1 && kv_dtype != 4) || max_pos > 8192 /* the engine's own limit; the tap's LDS strip grows with it */) return T3_E_INVALID;
     if (!have_device()) return T3_E_DEVICE;
     for (int r = 0; r < rows; ++r)
         if (row_stream[r] < 0 || row_stream[r] >= n_streams || row_pos[r] < 0 || row_pos[r] >= max_pos) return T3_E_INVALID;
-    const bool fp8 = kv_dtype == 1;
     const int max_blocks = (max_pos + KV_BLOCK - 1) / KV_BLOCK, nb = n_streams * max_blocks, span = hi - lo;
     std::vector<int> table(nb);
     for (int i = 0; i < nb; ++i) table[i] = (int)(((long)i * 7919 + 13) % nb);
@@ -227,15 +237,15 @@ extern "C" int t3k_attention_probs(const void* qkv, const int32_t* row_stream, c
     DevBuf dqkv, drec, dc, ds, dq, dkv, dout, dqr, dkvo;
     K_TRY(dqkv.from(qkv, (size_t)rows * QKV * 2)); K_TRY(drec.from(recs.data(), recs.size() * 4));
     K_TRY(dc.from(c.data(), c.size() * 4)); K_TRY(ds.from(s.data(), s.size() * 4));
-    K_TRY(dq.alloc((size_t)rows * D * 2)); K_TRY(dkv.alloc((size_t)nb * KV_BLOCK_ELEMS * (fp8 ? 1 : 2), true));
+    K_TRY(dq.alloc((size_t)rows * D * 2)); K_TRY(dkv.alloc((size_t)nb * kv_block_bytes(kv_dtype), true));
     K_TRY(dout.alloc((size_t)rows * span * 4, true)); K_TRY(dqr.alloc((size_t)rows * HD * 2, true));
     RopeArgs ra{dqkv.as<uint16_t>(), dq.as<uint16_t>(), dkv.as<uint16_t>(), drec.as<int>(), stride, dc.as<float>(), ds.as<float>(), rows};
-    K_TRY(fp8 ? launch_rope_kv_fp8(ra, nullptr) : launch_rope_kv(ra, nullptr));
+    K_TRY(rope_kv_of(kv_dtype, ra));
     // frames_per_slot = 0: the destination row is the frame word alone, i.e. the row index
     AlignArgs aa{dqkv.as<uint16_t>(), dkv.p, drec.as<int>(), stride, nullptr, dc.as<float>(), ds.as<float>(), dout.as<float>(), rows, head, lo, (max_pos + CHUNK - 1) / CHUNK,
                  0, span, 0, 1, 1.0f, dqr.as<uint16_t>()};
-    K_TRY(launch_alignment(aa, fp8, nullptr));
-    if (kv_out) { K_TRY(dkvo.alloc((size_t)rows * 2 * D * 2, true)); K_TRY((fp8 ? launch_kv_gather_fp8 : launch_kv_gather)(dkv.as<uint16_t>(), drec.as<int>(), stride, rows, dkvo.as<uint16_t>(), nullptr)); }
+    K_TRY(launch_alignment(aa, kv_dtype, nullptr));
+    if (kv_out) { K_TRY(dkvo.alloc((size_t)rows * 2 * D * 2, true)); K_TRY(kv_gather_of(kv_dtype, dkv.as<uint16_t>(), drec.as<int>(), stride, rows, dkvo.as<uint16_t>())); }
     K_TRY(hipDeviceSynchronize());
     K_TRY(hipMemcpy(out, dout.p, (size_t)rows * span * 4, hipMemcpyDeviceToHost));
     if (q_rot) K_TRY(hipMemcpy(q_rot, dqr.p, (size_t)rows * HD * 2, hipMemcpyDeviceToHost));
@@ -252,7 +262,7 @@ extern "C" int t3k_attention_probs(const void* qkv, const int32_t* row_stream, c
  * out [steps][rows][1024]; kv_new (nullable) [steps][rows][2][1024]: K (rotated) and V of the positions the launches wrote, read
  * back from the pool. */
 static int decode_attention_impl(const void* ctx_qkv, int32_t n_content, int32_t content_rows, const void* new_qkv, const int32_t* ctx,
-                                 int32_t rows, int32_t steps, int32_t max_pos, int32_t waves, void* out, void* kv_new, bool fp8) {
+                                 int32_t rows, int32_t steps, int32_t max_pos, int32_t waves, void* out, void* kv_new, int fmt) {
     if (!ctx_qkv || !new_qkv || !ctx || !out || rows <= 0 || steps <= 0 || n_content <= 0 || content_rows <= 0 || max_pos <= 0 ||
         (waves != 0 && waves != 4 && waves != 8)) return T3_E_INVALID;
     for (int r = 0; r < rows; ++r)
@@ -273,7 +283,7 @@ static int decode_attention_impl(const void* ctx_qkv, int32_t n_content, int32_t
     K_TRY(dctx.from(ctx_qkv, (size_t)n_content * content_rows * QKV * 2)); K_TRY(dnew.from(new_qkv, (size_t)steps * rows * QKV * 2));
     K_TRY(dc.from(c.data(), c.size() * 4)); K_TRY(ds.from(s.data(), s.size() * 4));
     K_TRY(dq.alloc((size_t)content_rows * D * 2));                     // rotated q of the fill rows: not used
-    K_TRY(dkv.alloc((size_t)nb * KV_BLOCK_ELEMS * (fp8 ? 1 : 2), true)); K_TRY(dout.alloc((size_t)steps * rows * D * 2, true));
+    K_TRY(dkv.alloc((size_t)nb * kv_block_bytes(fmt), true)); K_TRY(dout.alloc((size_t)steps * rows * D * 2, true));
     K_TRY(dkvn.alloc((size_t)steps * rows * 2 * D * 2, true));
     // ---- context fill: one rope_kv launch per stream over its content's rows (positions 0 .. ctx[r] - 2)
     std::vector<int> recs((size_t)content_rows * stride);
@@ -290,7 +300,7 @@ static int decode_attention_impl(const void* ctx_qkv, int32_t n_content, int32_t
         K_TRY(hipMemcpy(drec_fill.p, recs.data(), (size_t)n * stride * 4, hipMemcpyHostToDevice));
         RopeArgs ra{dctx.as<uint16_t>() + (size_t)(r % n_content) * content_rows * QKV, dq.as<uint16_t>(), dkv.as<uint16_t>(), drec_fill.as<int>(), stride,
                     dc.as<float>(), ds.as<float>(), n};
-        K_TRY(fp8 ? launch_rope_kv_fp8(ra, nullptr) : launch_rope_kv(ra, nullptr));
+        K_TRY(rope_kv_of(fmt, ra));
         K_TRY(hipDeviceSynchronize());                                 // the record buffer is reused by the next stream
     }
     // ---- the decode launches
@@ -306,8 +316,8 @@ static int decode_attention_impl(const void* ctx_qkv, int32_t n_content, int32_t
         AttnArgs aa{nullptr, dkv.as<uint16_t>(), drec.as<int>(), stride, dout.as<uint16_t>() + (size_t)st * rows * D, rows, (max_pos + CHUNK - 1) / CHUNK,
                     dnew.as<uint16_t>() + (size_t)st * rows * QKV, dkv.as<uint16_t>(), dc.as<float>(), ds.as<float>()};
         aa.force_waves = waves;
-        K_TRY(fp8 ? launch_attention_fp8(aa, nullptr) : launch_attention(aa, nullptr));
-        K_TRY((fp8 ? launch_kv_gather_fp8 : launch_kv_gather)(dkv.as<uint16_t>(), drec.as<int>(), stride, rows, dkvn.as<uint16_t>() + (size_t)st * rows * 2 * D, nullptr));
+        K_TRY(attention_of(fmt, aa));
+        K_TRY(kv_gather_of(fmt, dkv.as<uint16_t>(), drec.as<int>(), stride, rows, dkvn.as<uint16_t>() + (size_t)st * rows * 2 * D));
         K_TRY(hipDeviceSynchronize());
     }
     K_TRY(hipMemcpy(out, dout.p, (size_t)steps * rows * D * 2, hipMemcpyDeviceToHost));
@@ -316,11 +326,15 @@ static int decode_attention_impl(const void* ctx_qkv, int32_t n_content, int32_t
 }
 extern "C" int t3k_decode_attention(const void* ctx_qkv, int32_t n_content, int32_t content_rows, const void* new_qkv, const int32_t* ctx,
                                     int32_t rows, int32_t steps, int32_t max_pos, int32_t waves, void* out, void* kv_new) {
-    return decode_attention_impl(ctx_qkv, n_content, content_rows, new_qkv, ctx, rows, steps, max_pos, waves, out, kv_new, false);
+    return decode_attention_impl(ctx_qkv, n_content, content_rows, new_qkv, ctx, rows, steps, max_pos, waves, out, kv_new, 0);
 }
 extern "C" int t3k_decode_attention_fp8(const void* ctx_qkv, int32_t n_content, int32_t content_rows, const void* new_qkv, const int32_t* ctx,
                                         int32_t rows, int32_t steps, int32_t max_pos, int32_t waves, void* out, void* kv_new) {
-    return decode_attention_impl(ctx_qkv, n_content, content_rows, new_qkv, ctx, rows, steps, max_pos, waves, out, kv_new, true);
+    return decode_attention_impl(ctx_qkv, n_content, content_rows, new_qkv, ctx, rows, steps, max_pos, waves, out, kv_new, 1);
+}
+extern "C" int t3k_decode_attention_fp4(const void* ctx_qkv, int32_t n_content, int32_t content_rows, const void* new_qkv, const int32_t* ctx,
+                                        int32_t rows, int32_t steps, int32_t max_pos, int32_t waves, void* out, void* kv_new) {
+    return decode_attention_impl(ctx_qkv, n_content, content_rows, new_qkv, ctx, rows, steps, max_pos, waves, out, kv_new, 4);
 }
 
 static int sample_impl(const void* logits2, int32_t ldl, uint16_t* counts, const T3Sampling* sp, float cfg, uint32_t step,
@@ -407,6 +421,17 @@ extern "C" int t3k_fp8_roundtrip(const float* x, float* y, int32_t n) {
     DevBuf dx, dy;
     K_TRY(dx.from(x, (size_t)n * 4)); K_TRY(dy.alloc((size_t)n * 4));
     K_TRY(launch_fp8_roundtrip(dx.as<float>(), dy.as<float>(), n, nullptr));
+    K_TRY(hipDeviceSynchronize());
+    K_TRY(hipMemcpy(y, dy.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return T3_OK;
+}
+
+extern "C" int t3k_fp4_roundtrip(const float* x, float* y, int32_t n) {
+    if (!x || !y || n <= 0 || n % 32) return T3_E_INVALID;
+    if (!have_device()) return T3_E_DEVICE;
+    DevBuf dx, dy;
+    K_TRY(dx.from(x, (size_t)n * 4)); K_TRY(dy.alloc((size_t)n * 4));
+    K_TRY(launch_fp4_roundtrip(dx.as<float>(), dy.as<float>(), n, nullptr));
     K_TRY(hipDeviceSynchronize());
     K_TRY(hipMemcpy(y, dy.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     return T3_OK;

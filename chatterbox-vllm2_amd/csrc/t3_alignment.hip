@@ -8,10 +8,10 @@
 //     P[j] = softmax_j( q . K_j / 8 )      over the row's whole causal context j = 0 .. pos,      out[t] (+)= P[lo + t],  t < n_text
 //
 // with q the row's pre-RoPE query rotated here by rope8() with the table row the attention used (nothing rotated is read from anywhere, so
-// one path serves prefill-last-row, decode and mixed steps) and K as the pool stores it (bf16, or the dequantised E4M3 value).
+// one path serves prefill-last-row, decode and mixed steps) and K as the pool stores it (bf16, or the dequantised E4M3 / MXFP4 value).
 //
 // Split: one workgroup of 4 waves per sampled row; wave w takes the 64-token chunks w, w + 4, ...  A chunk's K is 8 fully coalesced 1 KiB
-// wave loads (FP8 pool: 4) straight into MFMA A operands; q is replicated over the 16 B columns (v_mfma_f32_16x16x32_bf16: the products
+// wave loads (FP8 pool: 4, MXFP4 pool: 2 and 8 scale bytes) straight into MFMA A operands; q is replicated over the 16 B columns (v_mfma_f32_16x16x32_bf16: the products
 // and the fp32 accumulation of the attention kernel).  No V is touched: a tap costs 128 B x context per row (FP8: 64 B).  Scores x 1/8 go
 // to an LDS strip [max_chunks x 64] fp32 with the per-chunk maxima beside it.  Behind a barrier M = max over chunks; every wave turns its own
 // chunks of the strip into e_j = t3_expf(s_j - M) IN PLACE and leaves the chunk's butterfly sum (contract pairing: xor 32, 16, 8, 4, 2, 1);
@@ -31,7 +31,7 @@
 
 namespace t3 {
 
-template <bool FP8>
+template <int FMT>      // T3EngineConfig.kv_cache_dtype: 0 bf16, 1 FP8 E4M3, 4 MXFP4
 __global__ __launch_bounds__(256) void alignment_kernel(AlignArgs a) {
     extern __shared__ __attribute__((aligned(16))) float strip[];      // [max_chunks][64] scores, then e | [max_chunks] chunk max | [max_chunks] chunk sum
     float* cm = strip + (size_t)a.max_chunks * CHUNK; float* cl = cm + a.max_chunks;
@@ -68,7 +68,15 @@ __global__ __launch_bounds__(256) void alignment_kernel(AlignArgs a) {
         const int npool = L - c * CHUNK;            // tokens of this chunk (wave-uniform; >= 64 except in the last chunk)
         uint4 kf[8];                                // A operands: fragment (tt, ds) at 2 tt + ds
         // of the context's last chunk only the fragments that hold tokens are requested; the rest are zeroed (their scores are masked)
-        if constexpr (FP8) {
+        if constexpr (FMT == 4) {
+            // two 16-byte pieces (token tiles 2 j, 2 j + 1) and the lane's eight scale bytes; the second piece only where it holds tokens
+            const uint8_t* Kb = reinterpret_cast<const uint8_t*>(a.kv_layer) + kv4_head_base(blk, 0, h) + (size_t)ci * CHUNK4_REC;
+            const uint4* Kp = reinterpret_cast<const uint4*>(Kb) + k_lane_piece(lane);
+            const uint4 k4[2] = {ld_nt(Kp), 32 < npool ? ld_nt(Kp + 64) : make_uint4(0, 0, 0, 0)};
+            const uint2 ks = *reinterpret_cast<const uint2*>(Kb + CHUNK4 + 8 * col);
+            kf[0] = k4_frag<0, 0>(k4, ks); kf[1] = k4_frag<0, 1>(k4, ks); kf[2] = k4_frag<1, 0>(k4, ks); kf[3] = k4_frag<1, 1>(k4, ks);
+            kf[4] = k4_frag<2, 0>(k4, ks); kf[5] = k4_frag<2, 1>(k4, ks); kf[6] = k4_frag<3, 0>(k4, ks); kf[7] = k4_frag<3, 1>(k4, ks);
+        } else if constexpr (FMT == 1) {
             const uint4* Kp = reinterpret_cast<const uint4*>(reinterpret_cast<const uint8_t*>(a.kv_layer) + kv8_head_base(blk, 0, h) + (size_t)ci * CHUNK8) + k8_lane_piece(lane);
 #pragma unroll
             for (int tt = 0; tt < 4; ++tt) {        // one 16-byte piece carries both halves (ds = 0, 1) of the lane's operands
@@ -127,12 +135,14 @@ __global__ __launch_bounds__(256) void alignment_kernel(AlignArgs a) {
     }
 }
 
-hipError_t launch_alignment(const AlignArgs& a, bool fp8, hipStream_t s) {
+hipError_t launch_alignment(const AlignArgs& a, int kv_dtype, hipStream_t s) {
     if (a.n_wg <= 0) return hipSuccess;
     const size_t lds = (size_t)a.max_chunks * (CHUNK + 2) * sizeof(float);      // 4.1 KiB at max_model_len 1000, 33 KiB at 8192: under the 64 KiB every kernel may ask for
     if (lds > 64 * 1024) return hipErrorInvalidValue;      // a context beyond 15 872 tokens: the engine stops at 8192 (t3_create), the parity hook checks max_pos
-    if (fp8) launch_k(alignment_kernel<true>, dim3(a.n_wg), dim3(256), lds, s, a);
-    else launch_k(alignment_kernel<false>, dim3(a.n_wg), dim3(256), lds, s, a);
+    if (kv_dtype == 4) launch_k(alignment_kernel<4>, dim3(a.n_wg), dim3(256), lds, s, a);
+    else if (kv_dtype == 1) launch_k(alignment_kernel<1>, dim3(a.n_wg), dim3(256), lds, s, a);
+    else if (kv_dtype == 0) launch_k(alignment_kernel<0>, dim3(a.n_wg), dim3(256), lds, s, a);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

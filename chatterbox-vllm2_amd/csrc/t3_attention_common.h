@@ -1,5 +1,6 @@
-// Device helpers the attention translation units share (t3_attention.hip: bf16 pool, t3_attention_fp8.hip: FP8 E4M3 pool, t3_alignment.hip:
-// the K-only probability tap over either): where a head's K / V live in the paged pool, the FP8 dequantisation, the RoPE of one lane's eight
+// Device helpers the attention translation units share (t3_attention.hip: bf16 pool, t3_attention_fp8.hip: FP8 E4M3 pool, t3_attention_fp4.hip:
+// MXFP4 pool, t3_alignment.hip: the K-only probability tap over any of them): where a head's K / V live in the paged pool, the FP8 and MXFP4
+// dequantisation, the RoPE of one lane's eight
 // rotation pairs and the wave reductions in the contract's order (DESIGN.md "Attention", "RoPE").  One copy, so every reader runs the same
 // addresses, products, roundings and pairings.
 #pragma once
@@ -28,6 +29,30 @@ __device__ __forceinline__ uint32_t dq8_pair(uint32_t w) {                      
 }
 __device__ __forceinline__ uint4 dq8_frag(uint32_t w0, uint32_t w1) {                // eight e4m3 bytes -> one MFMA operand fragment of eight bf16
     return make_uint4(dq8_pair<false>(w0), dq8_pair<true>(w0), dq8_pair<false>(w1), dq8_pair<true>(w1));
+}
+// ---- MXFP4 pool (layout and format: t3_attention_fp4.hip).  A head's chunk record is CHUNK4 data bytes followed by its 2 * CHUNK scale bytes.
+__device__ __forceinline__ size_t kv4_head_base(int blk, int kv, int h) {
+    return (size_t)blk * KV4_BLOCK_BYTES + (size_t)(kv * H + h) * KV4_HEAD_BYTES;
+}
+// E8M0 scale byte -> the fp32 operand of the scaled converts, 2^(b - 127); b = 0 is the fp32 subnormal 2^-127
+__device__ __forceinline__ float sc4(uint32_t b) { return __uint_as_float(max((b & 0xffu) << 23, 0x00400000u)); }
+template <int SEL>
+__device__ __forceinline__ uint32_t dq4_pair(uint32_t w, float scale) {              // the two E2M1 nibbles of byte SEL of w, times scale -> packed bf16 pair (exact)
+    union { bf16x2 v; uint32_t u; } c;
+    c.v = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, SEL);
+    return c.u;
+}
+__device__ __forceinline__ uint4 dq4_frag(uint32_t w, float scale) {                 // eight nibbles under one scale -> one MFMA operand fragment of eight bf16
+    return make_uint4(dq4_pair<0>(w, scale), dq4_pair<1>(w, scale), dq4_pair<2>(w, scale), dq4_pair<3>(w, scale));
+}
+// K of one chunk as lane (t = lane % 16, kg = lane / 16) holds it: k[j] = the 16-byte piece j (token tiles tt = 2 j, 2 j + 1: words ds = 0, 1 of each),
+// ks = the lane's eight scale bytes [tt][ds].  -> the A fragment of (tt, ds): dims 32 ds + 8 kg .. +7 of token 16 tt + t
+template <int TT, int DS>
+__device__ __forceinline__ uint4 k4_frag(const uint4 (&k)[2], const uint2& ks) {
+    const uint4& p = k[TT >> 1];
+    const uint32_t w = (TT & 1) ? (DS ? p.w : p.z) : (DS ? p.y : p.x);
+    const uint32_t s = (TT >> 1) ? ks.y : ks.x;
+    return dq4_frag(w, sc4(s >> (16 * (TT & 1) + 8 * DS)));
 }
 // RoPE (rotate-half, llama3-scaled table): pairs i in [8*part, 8*part+8):  o1 = x1*c - x2*s, o2 = x2*c + x1*s
 // (cos/sin are bf16-valued so both products are exact; one fp32 rounding, then bf16).

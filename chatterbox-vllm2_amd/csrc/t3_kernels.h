@@ -24,6 +24,14 @@ constexpr int KV_HEAD_PAD = T3_KV_PAD;               // elements of padding afte
 constexpr int KV_HEAD_ELEMS = KV_BLOCK * HD + KV_HEAD_PAD;
 constexpr int KV_BLOCK_ELEMS = 2 * H * KV_HEAD_ELEMS;  // per layer per block: [kv][head][chunk][8 fragments][64 lanes][8]
 
+// MXFP4 pool (t3_attention_fp4.hip, T3EngineConfig.kv_cache_dtype = 4), sized in BYTES: a head's 64-token chunk of K (or V) is CHUNK4 bytes of
+// E2M1 nibbles followed by its 2 * CHUNK E8M0 scale bytes; the head regions keep KV_HEAD_PAD elements (here half a byte each) between them.
+constexpr int CHUNK4 = CHUNK * HD / 2;
+constexpr int CHUNK4_REC = CHUNK4 + 2 * CHUNK;
+constexpr int KV4_HEAD_BYTES = (KV_BLOCK / CHUNK) * CHUNK4_REC + KV_HEAD_PAD / 2;
+constexpr int KV4_BLOCK_BYTES = 2 * H * KV4_HEAD_BYTES;     // per layer per block
+static_assert(KV4_HEAD_BYTES % 128 == 0, "a head region of the MXFP4 pool starts on a cache line");
+
 enum GemmEpi { EPI_F32 = 0, EPI_BF16 = 1, EPI_RESID = 2, EPI_SILU = 3 };
 
 // Weights of a LATER launch on the stream, pulled into the L2 of the XCD that will read them while this launch leaves the memory system
@@ -128,13 +136,19 @@ hipError_t launch_rope_kv_fp8(const RopeArgs& a, hipStream_t s);
 hipError_t launch_attention_fp8(const AttnArgs& a, hipStream_t s);
 hipError_t launch_kv_gather_fp8(const uint16_t* kv_layer, const int* rowrec, int row_stride, int rows, uint16_t* out, hipStream_t s);
 hipError_t launch_fp8_roundtrip(const float* x, float* y, int n, hipStream_t s);   // parity hook: y = dequantised q8(x)
+// And over an MXFP4 pool, t3_attention_fp4.hip (kv_cache_dtype = 4): kv_layer / kv_layer_w point at bytes, a layer of the pool is
+// n_blocks * KV4_BLOCK_BYTES of them.
+hipError_t launch_rope_kv_fp4(const RopeArgs& a, hipStream_t s);
+hipError_t launch_attention_fp4(const AttnArgs& a, hipStream_t s);
+hipError_t launch_kv_gather_fp4(const uint16_t* kv_layer, const int* rowrec, int row_stride, int rows, uint16_t* out, hipStream_t s);
+hipError_t launch_fp4_roundtrip(const float* x, float* y, int n, hipStream_t s);   // parity hook: y = the stored value of x, blocks of 32 (n a multiple of 32)
 
 // The alignment tap (t3_alignment.hip): attention probabilities of ONE head over the span [lo, lo + n_text) of each tapped row's context,
 // K only.  Workgroup i serves row sel_rows[2 i] (the conditional row of sampled utterance i; sel_rows null: row i) and leaves at once where
 // the row record's frame word is -1.  Destination: out[((stream / 2) * frames_per_slot + frame) * ld + t].
 struct AlignArgs {
     const uint16_t* qkv;       // [rows][3072] pre-RoPE: the step's qkv buffer
-    const void* kv_layer;      // the layer's pool (bf16, or one-byte E4M3 elements), holding the rows' newest K already
+    const void* kv_layer;      // the layer's pool (bf16, one-byte E4M3 elements, or MXFP4 bytes), holding the rows' newest K already
     const int* rowrec; int row_stride;
     const int* sel_rows;       // nullable
     const float *cos_t, *sin_t;
@@ -145,7 +159,7 @@ struct AlignArgs {
     int tap, n_taps; float inv_taps;     // tap 0 stores, later taps add, tap n_taps - 1 scales by inv_taps
     uint16_t* q_rot_out = nullptr;       // nullable (parity hook): [rows][64] the rotated q the tap used
 };
-hipError_t launch_alignment(const AlignArgs& a, bool fp8, hipStream_t s);
+hipError_t launch_alignment(const AlignArgs& a, int kv_dtype, hipStream_t s);   // kv_dtype: T3EngineConfig.kv_cache_dtype (0, 1, 4)
 hipError_t launch_alignment_clear(float* p, size_t n, hipStream_t s);   // p[0 .. n) = 0 by a kernel; n a multiple of 4, p 16-byte aligned
 
 struct SampleArgs {

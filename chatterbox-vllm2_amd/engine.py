@@ -99,6 +99,7 @@ ABI_SYMBOLS = [
     "t3_clean_tokens", "t3_debug_logits", "t3_step_times", "t3_stats", "t3_reset_stats", "t3_set_profile", "t3_set_profile_kernel", "t3_kernel_ms",
     "t3k_gemm", "t3k_norm_gemm", "t3k_qkv_gemm", "t3k_head_gemm", "t3k_gemm_resid", "t3k_silu_mul_gemm", "t3k_rope_attention", "t3k_decode_attention", "t3k_sample", "t3k_sample_support", "t3k_expf",
     "t3k_fp8_roundtrip", "t3k_rope_attention_fp8", "t3k_decode_attention_fp8",
+    "t3k_fp4_roundtrip", "t3k_rope_attention_fp4", "t3k_decode_attention_fp4",
     "t3_reserve_alignment", "t3_set_alignment_heads", "t3_get_alignment", "t3k_attention_probs",
     "t3_set_alignment_guard", "t3_get_guard", "t3k_alignment_guard", "t3k_sample_ctl",
     "t3_reserve_logprobs", "t3_request_logprobs", "t3_get_logprobs", "t3k_logprobs",
@@ -171,6 +172,9 @@ def load_library():
     L.t3k_fp8_roundtrip.argtypes = [vp, vp, i32]
     L.t3k_rope_attention_fp8.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     L.t3k_decode_attention_fp8.argtypes = [vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp]
+    L.t3k_fp4_roundtrip.argtypes = [vp, vp, i32]
+    L.t3k_rope_attention_fp4.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
+    L.t3k_decode_attention_fp4.argtypes = [vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp]
     L.t3_reserve_alignment.argtypes = [vp, i32]
     L.t3_set_alignment_heads.argtypes = [vp, vp, i32]
     L.t3_get_alignment.argtypes = [vp, i64, vp, ct.POINTER(i32), ct.POINTER(i32)]
@@ -225,7 +229,7 @@ def make_sampling(temperature=0.8, top_p=1.0, min_p=0.0, repetition_penalty=2.0,
 
 
 # storage formats of the paged KV pool (T3EngineConfig.kv_cache_dtype), under vLLM's names for them
-KV_CACHE_DTYPES = {"auto": 0, "bfloat16": 0, "bf16": 0, "fp8": 1, "fp8_e4m3": 1}
+KV_CACHE_DTYPES = {"auto": 0, "bfloat16": 0, "bf16": 0, "fp8": 1, "fp8_e4m3": 1, "mxfp4": 4, "fp4": 4}
 
 
 def kv_cache_dtype_code(name) -> int:
@@ -233,7 +237,7 @@ def kv_cache_dtype_code(name) -> int:
     if name is None:
         name = os.environ.get("T3_KV_CACHE_DTYPE", "bf16")
     if name not in KV_CACHE_DTYPES:
-        raise ValueError(f"kv_cache_dtype {name!r}: the T3 engine stores bf16 ('auto', 'bfloat16') or FP8 E4M3 ('fp8', 'fp8_e4m3')")
+        raise ValueError(f"kv_cache_dtype {name!r}: the T3 engine stores bf16 ('auto', 'bfloat16'), FP8 E4M3 ('fp8', 'fp8_e4m3') or MXFP4 ('mxfp4', 'fp4')")
     return KV_CACHE_DTYPES[name]
 
 
@@ -635,6 +639,37 @@ def k_decode_attention_fp8(ctx_qkv: torch.Tensor, new_qkv: torch.Tensor, ctx, ma
     out = torch.empty(steps, rows, C.HIDDEN, dtype=torch.bfloat16); kvn = torch.empty(steps, rows, 2, C.HIDDEN, dtype=torch.bfloat16)
     _chk_k(load_library().t3k_decode_attention_fp8(ctx_qkv.data_ptr(), ctx_qkv.shape[0], ctx_qkv.shape[1], new_qkv.data_ptr(), cx.ctypes.data,
                                                    rows, steps, int(max_pos), int(waves), out.data_ptr(), kvn.data_ptr()), "t3k_decode_attention_fp8")
+    return out, kvn
+
+
+def k_fp4_roundtrip(x: torch.Tensor) -> torch.Tensor:
+    """The stored format of the MXFP4 KV pool over the last axis in blocks of 32: quantise on the device and back (fp32 in, fp32 out)."""
+    x = x.to(torch.float32).contiguous()
+    assert x.numel() % 32 == 0
+    y = torch.empty_like(x)
+    _chk_k(load_library().t3k_fp4_roundtrip(x.data_ptr(), y.data_ptr(), x.numel()), "t3k_fp4_roundtrip")
+    return y
+
+
+def k_rope_attention_fp4(qkv: torch.Tensor, row_stream, row_pos, n_streams: int, max_pos: int):
+    """k_rope_attention over an MXFP4 pool -> (out [rows, 1024] bf16, stored K / V of every row's position, dequantised [rows, 2, 1024] bf16)"""
+    qkv = _bf(qkv)
+    rs = np.ascontiguousarray(np.asarray(row_stream, dtype=np.int32)); rp = np.ascontiguousarray(np.asarray(row_pos, dtype=np.int32))
+    out = torch.empty(qkv.shape[0], C.HIDDEN, dtype=torch.bfloat16); kvo = torch.empty(qkv.shape[0], 2, C.HIDDEN, dtype=torch.bfloat16)
+    _chk_k(load_library().t3k_rope_attention_fp4(qkv.data_ptr(), rs.ctypes.data, rp.ctypes.data, qkv.shape[0], n_streams, max_pos,
+                                                 out.data_ptr(), kvo.data_ptr()), "t3k_rope_attention_fp4")
+    return out, kvo
+
+
+def k_decode_attention_fp4(ctx_qkv: torch.Tensor, new_qkv: torch.Tensor, ctx, max_pos: int, waves: int = 0):
+    """k_decode_attention over an MXFP4 pool: same arguments, kv_new read back dequantised."""
+    ctx_qkv, new_qkv = _bf(ctx_qkv), _bf(new_qkv)
+    cx = np.ascontiguousarray(np.asarray(ctx, dtype=np.int32))
+    steps, rows = new_qkv.shape[0], new_qkv.shape[1]
+    assert ctx_qkv.dim() == 3 and ctx_qkv.shape[2] == 3072 and new_qkv.shape[2] == 3072 and len(cx) == rows
+    out = torch.empty(steps, rows, C.HIDDEN, dtype=torch.bfloat16); kvn = torch.empty(steps, rows, 2, C.HIDDEN, dtype=torch.bfloat16)
+    _chk_k(load_library().t3k_decode_attention_fp4(ctx_qkv.data_ptr(), ctx_qkv.shape[0], ctx_qkv.shape[1], new_qkv.data_ptr(), cx.ctypes.data,
+                                                   rows, steps, int(max_pos), int(waves), out.data_ptr(), kvn.data_ptr()), "t3k_decode_attention_fp4")
     return out, kvn
 
 

@@ -140,7 +140,8 @@ class LLM:
         if dtype not in ("bfloat16", "auto", torch.bfloat16):
             raise ValueError("the T3 engine computes in bf16 storage / fp32 accumulation only")
         # vLLM's switch for the storage format of the KV cache ("auto" / "bfloat16": bf16; "fp8" / "fp8_e4m3": E4M3 with scale 1.0, half
-        # the bytes per token; anything else, "fp8_e5m2" included, is a ValueError).  None: the T3_KV_CACHE_DTYPE environment variable.
+        # the bytes per token; "mxfp4" / "fp4": E2M1 with one power-of-two scale per 32 head dims of a token, 1088 bytes per token and layer
+        # against 4096; anything else, "fp8_e5m2" included, is a ValueError).  None: the T3_KV_CACHE_DTYPE environment variable.
         kv_cache_dtype_code(kv_cache_dtype)
         for k in kwargs:
             warnings.warn(f"LLM(...) keyword {k!r} has no meaning for the T3 engine and is ignored")

@@ -53,8 +53,9 @@ typedef struct {
     int32_t debug_logits;      /* 1: keep post-CFG logits of each sampled step for t3_debug_logits */
     int32_t n_groups;          /* utterance groups run concurrently on separate HIP streams; 0 = auto */
     int32_t kv_cache_dtype;    /* storage format of the paged KV pool: 0 = bf16 (default), 1 = FP8 E4M3FN with scale 1.0 (vLLM's
-                                  kv_cache_dtype="fp8": half the bytes per token); any other value is T3_E_INVALID.  This was padding:
-                                  a C caller must zero it */
+                                  kv_cache_dtype="fp8": half the bytes per token), 4 = MXFP4 (E2M1 elements, one E8M0 scale per 32 head
+                                  dims of one token: 1088 bytes per token and layer against 4096); any other value, 2 and 3 included,
+                                  is T3_E_INVALID.  This was padding: a C caller must zero it */
 } T3EngineConfig;
 
 /* Replaces vllm.SamplingParams as configured at tts.py:455-464 (+ the kwargs it forwards). */
@@ -379,8 +380,17 @@ int t3k_rope_attention_fp8(const void* qkv_bf16, const int32_t* row_stream, cons
 /* t3k_decode_attention over an FP8 pool: same arguments and meaning, kv_new read back dequantised. */
 int t3k_decode_attention_fp8(const void* ctx_qkv_bf16, int32_t n_content, int32_t content_rows, const void* new_qkv_bf16, const int32_t* ctx,
                              int32_t rows, int32_t steps, int32_t max_pos, int32_t waves, void* out_bf16, void* kv_new_bf16);
+/* ---- the MXFP4 KV pool, kv_cache_dtype = 4 ----
+ * y = the stored value of x on the device, over blocks of 32 consecutive values (n a multiple of 32): with E the biased exponent field of the
+ * block's max |x|, b = max(E - 2, 0) and X = 2^(b - 127), y = X * E2M1(round-to-nearest-even(x / X)), saturating at +-6. */
+int t3k_fp4_roundtrip(const float* x, float* y, int32_t n);
+/* t3k_rope_attention / t3k_decode_attention over an MXFP4 pool: the arguments and meaning of the FP8 pair above. */
+int t3k_rope_attention_fp4(const void* qkv_bf16, const int32_t* row_stream, const int32_t* row_pos, int32_t rows,
+                           int32_t n_streams, int32_t max_pos, void* out_bf16, void* kv_bf16);
+int t3k_decode_attention_fp4(const void* ctx_qkv_bf16, int32_t n_content, int32_t content_rows, const void* new_qkv_bf16, const int32_t* ctx,
+                             int32_t rows, int32_t steps, int32_t max_pos, int32_t waves, void* out_bf16, void* kv_new_bf16);
 /* The alignment tap kernel (t3_alignment.hip) on host buffers.  Every row is written through the prefill path (RoPE + paged write, as
- * t3k_rope_attention / t3k_rope_attention_fp8 do; kv_dtype 0 = bf16 pool, 1 = FP8), then the tap runs for EVERY row over the span [lo, hi) of
+ * t3k_rope_attention / t3k_rope_attention_fp8 / _fp4 do; kv_dtype 0 = bf16 pool, 1 = FP8, 4 = MXFP4), then the tap runs for EVERY row over the span [lo, hi) of
  * its stream: out [rows][hi - lo] = softmax over the row's context 0 .. row_pos of head `head`; positions at or beyond the row's own context
  * length come back as 0.  q_rot (nullable) bf16 [rows][64] = the rotated q the tap used; kv (nullable) bf16 [rows][2][1024] = the stored K / V
  * of every row's position (dequantised for the FP8 pool). */
