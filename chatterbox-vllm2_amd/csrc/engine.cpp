@@ -167,6 +167,8 @@ struct T3Engine {
     std::vector<void*> out_slabs;      // the allocations the pool was carved from
     HandoffItem* d_handoff_items = nullptr; int handoff_items_cap = 0;      // persistent argument buffer of t3_handoff_tokens
     hipEvent_t ev_handoff = nullptr;
+    // token spans (t3_get_token_spans, t3_align_path.hip): one workspace for a call's items, back-pointer words, paths and results; grows on demand
+    char* d_span_ws = nullptr; size_t span_ws_cap = 0;
     // alignment export (t3_reserve_alignment): per slot [max_model_len frames][align_ld] fp32, row k = what the taps' heads pay to the text
     // positions while token k is drawn (t3_alignment.hip).  Rows are align_ld = max_text rounded up to 4 floats apart.
     float* d_align = nullptr; int align_max_text = 0, align_ld = 0;
@@ -290,7 +292,7 @@ extern "C" int t3_destroy(T3Handle e) {
     }
     free_dev(e->d_cond); free_dev(e->d_counts); free_dev(e->d_sp); free_dev(e->d_dbg); free_dev(e->d_hist);
     for (void* b : e->out_slabs) free_dev(b);      // every hand-off buffer (pooled or held by a request) lives in one of these
-    free_dev(e->d_handoff_items); free_dev(e->d_dbg_emb);
+    free_dev(e->d_handoff_items); free_dev(e->d_dbg_emb); free_dev(e->d_span_ws);
     free_dev(e->d_align); free_dev(e->d_guard_state); free_dev(e->d_guard_ctl);
     for (float* b : e->align_pool) free_dev(b);
     free_dev(e->d_lp_rec); free_dev(e->d_lp_k);
@@ -1255,6 +1257,62 @@ extern "C" int t3_get_alignment(T3Handle e, int64_t req_id, float* out, int32_t*
     std::vector<float> rows((size_t)nf * r.align_ld);
     HIP_TRY(hipMemcpy(rows.data(), r.d_align, rows.size() * 4, hipMemcpyDeviceToHost));
     for (int k = 0; k < nf; ++k) memcpy(out + (size_t)k * nt, rows.data() + (size_t)k * r.align_ld, (size_t)nt * 4);
+    return T3_OK;
+}
+
+// ---- token time spans from the alignment matrix ------------------------------------------------------------
+extern "C" int t3_get_token_spans(T3Handle e, const int64_t* req_ids, int32_t n, int32_t ld, int32_t* start, int32_t* end, int32_t* n_text,
+                                  int32_t* last, int32_t* score) {
+    if (!e || !req_ids || !start || !end || n <= 0 || ld <= 0) return T3_E_INVALID;
+    std::vector<AlignPathItem> items(n);
+    // workspace: items | per request: back-pointer words [nf][ceil(nt / 64)], path [nf] | start [n][ld] | end [n][ld] | (last, score) [n]
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    size_t off = up((size_t)n * sizeof(AlignPathItem));
+    std::vector<size_t> bp_off(n), path_off(n);
+    int max_text = 0;
+    for (int i = 0; i < n; ++i) {
+        auto it = e->reqs.find(req_ids[i]);
+        if (it == e->reqs.end()) return e->fail(T3_E_NOTFOUND, "unknown request id");
+        const Request& r = it->second;
+        if (!r.sp.alignment) return e->fail(T3_E_INVALID, "request " + std::to_string(req_ids[i]) + " was not submitted with alignment >= 1");
+        if (r.state != FINISHED) return e->fail(T3_E_STATE, "request " + std::to_string(req_ids[i]) + " has not finished");
+        const int nf = (int)r.out.size(), nt = (int)r.prompt.size() - 1 - T3_COND_ROWS;
+        if (nt > ld) return e->fail(T3_E_INVALID, "token spans: ld = " + std::to_string(ld) + " is smaller than the " + std::to_string(nt) + " text tokens of request " + std::to_string(req_ids[i]));
+        if (nf > ALIGN_PATH_MAX_FRAMES || nt > ALIGN_PATH_MAX_TEXT) return e->fail(T3_E_INVALID, "token spans: more than 8192 frames or 2112 text tokens");
+        if (nf > 0 && nt > 0 && !r.d_align) return e->fail(T3_E_DEVICE, "the alignment matrix of request " + std::to_string(req_ids[i]) + " could not be kept");
+        if (n_text) n_text[i] = nt;
+        max_text = std::max(max_text, nt);
+        bp_off[i] = off; off += up((size_t)nf * ((nt + 63) / 64) * 8);
+        path_off[i] = off; off += up((size_t)nf * 4);
+        items[i] = AlignPathItem{r.d_align, nf, nt, r.align_ld, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
+    }
+    const size_t se_off = off, res_off = se_off + up((size_t)2 * n * ld * 4), total = res_off + up((size_t)n * 8);
+    (void)hipSetDevice(e->cfg.device_id);
+    // the per-request copies of the matrices were queued on the group streams: this launch waits for them on the device, not on the host
+    for (auto& g : e->groups) { HIP_TRY(hipEventRecord(e->ev_handoff, g.stream)); HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_handoff, 0)); }
+    if (total > e->span_ws_cap) {
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        free_dev(e->d_span_ws); e->d_span_ws = nullptr; e->span_ws_cap = 0;
+        const size_t cap = total + total / 2;
+        if (hipMalloc((void**)&e->d_span_ws, cap) != hipSuccess) { e->d_span_ws = nullptr; return e->fail(T3_E_NOMEM, "hipMalloc of " + std::to_string(cap) + " bytes for the token-span workspace failed"); }
+        e->span_ws_cap = cap;
+    }
+    char* ws = e->d_span_ws;
+    int* d_start = reinterpret_cast<int*>(ws + se_off); int* d_end = d_start + (size_t)n * ld; int* d_res = reinterpret_cast<int*>(ws + res_off);
+    for (int i = 0; i < n; ++i) {
+        items[i].bp = reinterpret_cast<unsigned long long*>(ws + bp_off[i]); items[i].path = reinterpret_cast<int*>(ws + path_off[i]);
+        items[i].start = d_start + (size_t)i * ld; items[i].end = d_end + (size_t)i * ld; items[i].res = d_res + 2 * i;
+    }
+    HIP_TRY(hipMemcpyAsync(ws, items.data(), items.size() * sizeof(AlignPathItem), hipMemcpyHostToDevice, e->stream));   // pageable source: staged before the call returns
+    HIP_TRY(launch_align_path(reinterpret_cast<const AlignPathItem*>(ws), n, max_text, ld, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpy(start, d_start, (size_t)n * ld * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(end, d_end, (size_t)n * ld * 4, hipMemcpyDeviceToHost));
+    if (last || score) {
+        std::vector<int> res((size_t)2 * n);
+        HIP_TRY(hipMemcpy(res.data(), d_res, res.size() * 4, hipMemcpyDeviceToHost));
+        for (int i = 0; i < n; ++i) { if (last) last[i] = res[2 * i]; if (score) score[i] = res[2 * i + 1]; }
+    }
     return T3_OK;
 }
 

@@ -479,3 +479,38 @@ extern "C" int t3k_alignment_guard(const float* A, int32_t n_frames, int32_t n_t
     guard_unpack_state(words, final_state);
     return T3_OK;
 }
+
+/* The path kernel (t3_align_path.hip) on one host matrix: the launch the engine makes for a finished request, with a workspace of its own. */
+extern "C" int t3k_align_path(const float* A, int32_t n_frames, int32_t n_text, int32_t ld, int32_t* path, int32_t* start, int32_t* end,
+                              int32_t* last, int32_t* score) {
+    if (!A || !path || !start || !end || !last || !score || n_frames <= 0 || n_frames > ALIGN_PATH_MAX_FRAMES || n_text <= 0 ||
+        n_text > ALIGN_PATH_MAX_TEXT || ld < n_text) return T3_E_INVALID;
+    if (!have_device()) return T3_E_DEVICE;
+    const int ns = (n_text + 63) / 64;
+    DevBuf dA, dbp, dpath, dse, dres, ditem;
+    K_TRY(dA.from(A, (size_t)n_frames * ld * 4)); K_TRY(dbp.alloc((size_t)n_frames * ns * 8, true)); K_TRY(dpath.alloc((size_t)n_frames * 4, true));
+    K_TRY(dse.alloc((size_t)2 * n_text * 4)); K_TRY(dres.alloc(8, true));
+    const AlignPathItem item{dA.as<float>(), n_frames, n_text, ld, 0, dbp.as<unsigned long long>(), dpath.as<int>(), dse.as<int>(), dse.as<int>() + n_text, dres.as<int>()};
+    K_TRY(ditem.from(&item, sizeof(item)));
+    K_TRY(launch_align_path(ditem.as<AlignPathItem>(), 1, n_text, n_text, nullptr));
+    K_TRY(hipDeviceSynchronize());
+    int res[2];
+    K_TRY(hipMemcpy(path, dpath.p, (size_t)n_frames * 4, hipMemcpyDeviceToHost));
+    K_TRY(hipMemcpy(start, dse.p, (size_t)n_text * 4, hipMemcpyDeviceToHost));
+    K_TRY(hipMemcpy(end, dse.as<int>() + n_text, (size_t)n_text * 4, hipMemcpyDeviceToHost));
+    K_TRY(hipMemcpy(res, dres.p, 8, hipMemcpyDeviceToHost));
+    *last = res[0]; *score = res[1];
+    return T3_OK;
+}
+
+/* the cell score of the path kernel alone: w[i] = round(1024 log2 a'[i]) */
+extern "C" int t3k_align_scores(const float* a, int32_t* w, int32_t n) {
+    if (!a || !w || n <= 0) return T3_E_INVALID;
+    if (!have_device()) return T3_E_DEVICE;
+    DevBuf da, dw;
+    K_TRY(da.from(a, (size_t)n * 4)); K_TRY(dw.alloc((size_t)n * 4));
+    K_TRY(launch_align_scores(da.as<float>(), dw.as<int>(), n, nullptr));
+    K_TRY(hipDeviceSynchronize());
+    K_TRY(hipMemcpy(w, dw.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return T3_OK;
+}

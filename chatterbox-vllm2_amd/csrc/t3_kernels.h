@@ -216,6 +216,19 @@ struct LogprobArgs {
 };
 hipError_t launch_logprobs(const LogprobArgs& a, hipStream_t s);
 hipError_t launch_logprobs_mark(int* lp_k, int slot, int k, hipStream_t s);     // lp_k[slot] = k, by a kernel
+// Token time spans (t3_align_path.hip): one wave per request runs the monotonic path search of DESIGN.md section 8 over a finished alignment
+// matrix and leaves, per text id, the [start, end) frames the path spends on it.
+struct AlignPathItem {
+    const float* A;            // [n_frames][ld] fp32, columns >= n_text are never read into a result
+    int n_frames, n_text, ld, _pad;
+    unsigned long long* bp;    // workspace [n_frames][ceil(n_text / 64)]: bit l of word j of row k = cell (k, 64 j + l) came from t - 1
+    int* path;                 // [n_frames]
+    int* start; int* end;      // [span_ld] each: -1 beyond the path's last id
+    int* res;                  // [2]: last, score
+};
+constexpr int ALIGN_PATH_MAX_TEXT = 2112, ALIGN_PATH_MAX_FRAMES = 8192;      // 33 slots of 64 ids; 8192 x 65536 stays below 2^30
+hipError_t launch_align_path(const AlignPathItem* items /*device [n]*/, int n, int max_text /*over the items*/, int span_ld, hipStream_t s);
+hipError_t launch_align_scores(const float* a, int* w, int n, hipStream_t s);
 // Profile mode: the next single-kernel launch of this thread (decode GEMM forms, fused / per-row attention, embed, sampler) takes these as
 // its start / stop events (hipExtLaunchKernelGGL); launch_events_armed() afterwards tells whether a launcher consumed them.
 void arm_launch_events(hipEvent_t start, hipEvent_t stop);

@@ -103,6 +103,7 @@ ABI_SYMBOLS = [
     "t3_reserve_alignment", "t3_set_alignment_heads", "t3_get_alignment", "t3k_attention_probs",
     "t3_set_alignment_guard", "t3_get_guard", "t3k_alignment_guard", "t3k_sample_ctl",
     "t3_reserve_logprobs", "t3_request_logprobs", "t3_get_logprobs", "t3k_logprobs",
+    "t3_get_token_spans", "t3k_align_path", "t3k_align_scores",
     "t3_cond_create", "t3_cond_destroy", "t3_cond_last_error", "t3_cond_load_tensor", "t3_cond_encode", "t3_cond_emotion_row",
     "t3k_ce_layernorm", "t3k_ce_linear", "t3k_ce_attention", "t3k_set_prefill_rows", "t3k_set_prefill_wide_rows",
 ]
@@ -187,6 +188,9 @@ def load_library():
     L.t3_request_logprobs.argtypes = [vp, i64, i32]
     L.t3_get_logprobs.argtypes = [vp, i64, vp, vp, vp, vp, ct.POINTER(i32), ct.POINTER(i32)]
     L.t3k_logprobs.argtypes = [vp, i32, ct.c_float, i32, i32, ct.POINTER(i32), ct.POINTER(ct.c_float), vp, vp]
+    L.t3_get_token_spans.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp]
+    L.t3k_align_path.argtypes = [vp, i32, i32, i32, vp, vp, vp, ct.POINTER(i32), ct.POINTER(i32)]
+    L.t3k_align_scores.argtypes = [vp, vp, i32]
     L.t3_cond_create.argtypes = [i32, ct.POINTER(vp)]
     L.t3_cond_destroy.argtypes = [vp]
     L.t3_cond_last_error.restype = ct.c_char_p; L.t3_cond_last_error.argtypes = [vp]
@@ -380,6 +384,25 @@ class T3Engine:
         out = torch.zeros(int(nf.value), int(nt.value), dtype=torch.float32)
         self._chk(self.lib.t3_get_alignment(self.h, int(req_id), ct.c_void_p(out.data_ptr()), ct.byref(nf), ct.byref(nt)))
         return out
+
+    def get_token_spans(self, req_ids: Sequence[int]):
+        """When each text token is spoken: for finished, unreleased requests submitted with alignment (or the guard), one kernel launch
+        (csrc/t3_align_path.hip) runs the monotonic path search over their alignment matrices on the device.  Returns one
+        (spans int32 [n_text, 2] CPU tensor of [start, end) frames, -1 beyond the path's last id; last; score) per request.  Seconds = frame / 25."""
+        rid = np.ascontiguousarray(np.asarray(req_ids, dtype=np.int64))
+        n = len(rid)
+        if n == 0:
+            return []
+        ld = 1
+        for r in rid:
+            nf = ct.c_int32(0); nt = ct.c_int32(0)
+            self._chk(self.lib.t3_get_alignment(self.h, int(r), None, ct.byref(nf), ct.byref(nt)))
+            ld = max(ld, int(nt.value))
+        start = np.zeros((n, ld), dtype=np.int32); end = np.zeros((n, ld), dtype=np.int32)
+        nt = np.zeros(n, dtype=np.int32); last = np.zeros(n, dtype=np.int32); score = np.zeros(n, dtype=np.int32)
+        self._chk(self.lib.t3_get_token_spans(self.h, rid.ctypes.data, n, ld, start.ctypes.data, end.ctypes.data, nt.ctypes.data, last.ctypes.data,
+                                              score.ctypes.data))
+        return [(torch.from_numpy(np.stack([start[i, :nt[i]], end[i, :nt[i]]], axis=1)), int(last[i]), int(score[i])) for i in range(n)]
 
     def set_alignment_guard(self, params=True):
         """Enable the alignment guard (True = default parameters, or a dict of overrides) or, with None / False, disable it.  Only while
@@ -589,6 +612,26 @@ def k_alignment_guard(A: torch.Tensor, n_text: int, tok, params=None):
     ctl = np.zeros(n, dtype=np.int32); st = T3GuardState(); p = make_guard_params(params)
     _chk_k(load_library().t3k_alignment_guard(A.data_ptr(), n, int(n_text), A.shape[1], t.ctypes.data, ct.byref(p), ctl.ctypes.data, ct.byref(st)), "t3k_alignment_guard")
     return ctl.tolist(), guard_state_dict(st)
+
+
+def k_align_path(A: torch.Tensor, n_text: int):
+    """The path kernel of get_token_spans on A [n_frames, ld] fp32 (columns >= n_text are padding)
+    -> (path int32 [n_frames], start int32 [n_text], end int32 [n_text], last, score)."""
+    A = A.to(torch.float32).contiguous()
+    n = A.shape[0]
+    path = np.zeros(n, dtype=np.int32); start = np.zeros(n_text, dtype=np.int32); end = np.zeros(n_text, dtype=np.int32)
+    last = ct.c_int32(0); score = ct.c_int32(0)
+    _chk_k(load_library().t3k_align_path(A.data_ptr(), n, int(n_text), A.shape[1], path.ctypes.data, start.ctypes.data, end.ctypes.data,
+                                         ct.byref(last), ct.byref(score)), "t3k_align_path")
+    return path, start, end, int(last.value), int(score.value)
+
+
+def k_align_scores(a) -> np.ndarray:
+    """The path kernel's cell score: int32 rint(1024 log2 a') per element of a float32 array."""
+    a = np.ascontiguousarray(np.asarray(a, dtype=np.float32))
+    w = np.zeros(a.size, dtype=np.int32)
+    _chk_k(load_library().t3k_align_scores(a.ctypes.data, w.ctypes.data, a.size), "t3k_align_scores")
+    return w
 
 
 def k_sample_ctl(logits2: torch.Tensor, counts: torch.Tensor, sp: T3Sampling, cfg: float, step: int, ctl: int) -> int:

@@ -48,7 +48,7 @@ class SamplingParams:
                  repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
                  seed: Optional[int] = None, stop_token_ids: Optional[List[int]] = None, max_tokens: Optional[int] = 16,
                  ignore_eos: bool = False, pos_policy: int = 0, alignment: bool = False,
-                 alignment_guard: Union[bool, dict, None] = False, logprobs: Optional[int] = None, **kwargs):
+                 alignment_guard: Union[bool, dict, None] = False, logprobs: Optional[int] = None, timestamps: bool = False, **kwargs):
         for k, v in kwargs.items():
             if k not in self._IGNORED:
                 raise TypeError(f"SamplingParams got an unexpected keyword argument {k!r}")
@@ -95,6 +95,10 @@ class SamplingParams:
             self.alignment_guard = dict(alignment_guard) if isinstance(alignment_guard, dict) else {}
             self.alignment = True
 
+        # extension: when each text token is spoken (CompletionOutput.timestamps), from a path search over the alignment matrix on the device
+        # (csrc/t3_align_path.hip).  The request runs with the alignment tap on; the matrix itself is fetched only with alignment=True.
+        self.timestamps = bool(timestamps)
+
     def __repr__(self):
         return ("SamplingParams(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in (
             "temperature", "top_p", "top_k", "min_p", "repetition_penalty", "seed", "stop_token_ids", "max_tokens", "ignore_eos")) + ")")
@@ -110,6 +114,7 @@ class CompletionOutput:
     finish_reason: Optional[str] = None
     stop_reason: Union[int, str, None] = None
     alignment: Optional[torch.Tensor] = None      # SamplingParams(alignment=True): CPU float32 [n_tokens, n_text], row k = frame k's attention over the text
+    timestamps: Optional[torch.Tensor] = None     # SamplingParams(timestamps=True): CPU int32 [n_text, 2], [start, end) frames of every text id (25 frames / s), -1 = not reached
     guard: Optional[dict] = None                  # SamplingParams(alignment_guard=...): the guard's final state (T3Engine.get_guard); reason None = never forced
 
 
@@ -261,7 +266,9 @@ class LLM:
             if keep_for_handoff and not kept_before:
                 self.engine.reserve_handoff(0)      # finished requests keep the buffers they hold; no new ones are made
         outs = []
-        for rid, text, final, tap, guarded, want_lp in metas:
+        stamped = [m[0] for m in metas if m[6]]
+        spans = dict(zip(stamped, self.engine.get_token_spans(stamped)))      # one launch for all of the call's marked requests, before any is released
+        for rid, text, final, tap, guarded, want_lp, _ in metas:
             toks, fr = self.engine.get_output(rid)
             align = self.engine.get_alignment(rid) if tap else None
             guard = self.engine.get_guard(rid) if guarded else None
@@ -280,6 +287,7 @@ class LLM:
             outs.append(RequestOutput(request_id=str(rid), prompt=text, prompt_token_ids=final,
                                       outputs=[CompletionOutput(index=0, text="", token_ids=toks, finish_reason=reason,
                                                                 stop_reason=(toks[-1] if fr == 1 else None), alignment=align, guard=guard,
+                                                                timestamps=spans[rid][0] if rid in spans else None,
                                                                 logprobs=lps, cumulative_logprob=cum)]))
         return outs
 
@@ -300,7 +308,7 @@ class LLM:
 
     def _queue(self, prompts, sps, uids, metas, queued):
         texts = [self._text_ids(p) for p in prompts]
-        tapped = [len(t[1]) for t, sp in zip(texts, sps) if sp.alignment]      # text ids per tapped request
+        tapped = [len(t[1]) for t, sp in zip(texts, sps) if sp.alignment or sp.timestamps]      # text ids per tapped request
         if tapped and max(tapped) > self.engine.alignment_max_text:
             self.engine.reserve_alignment(max(tapped))
         guards = [sp.alignment_guard for sp in sps if sp.alignment_guard is not None]
@@ -331,14 +339,14 @@ class LLM:
             esp = make_sampling(temperature=sp.temperature, top_p=sp.top_p, min_p=sp.min_p, repetition_penalty=sp.repetition_penalty,
                                 presence_penalty=sp.presence_penalty, frequency_penalty=sp.frequency_penalty,
                                 top_k=max(0, sp.top_k), max_tokens=max_tokens, ignore_eos=sp.ignore_eos, stop_token=stop,
-                                seed=self.seed if sp.seed is None else sp.seed, uid=uid, pos_policy=sp.pos_policy, alignment=sp.alignment,
+                                seed=self.seed if sp.seed is None else sp.seed, uid=uid, pos_policy=sp.pos_policy, alignment=sp.alignment or sp.timestamps,
                                 alignment_guard=sp.alignment_guard is not None)
             rid = self._next_id; self._next_id += 1
             self.engine.add_request(rid, final, cond, esp)
             queued.append(rid)
             if sp.logprobs is not None:
                 self.engine.request_logprobs(rid, sp.logprobs)
-            metas.append((rid, text, final, sp.alignment, sp.alignment_guard is not None, sp.logprobs is not None))
+            metas.append((rid, text, final, sp.alignment, sp.alignment_guard is not None, sp.logprobs is not None, sp.timestamps))
 
     def shutdown(self):
         self.engine.close()

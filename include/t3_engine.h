@@ -201,6 +201,17 @@ int t3_set_alignment_heads(T3Handle h, const int32_t* layer_head_pairs, int32_t 
  * returns, n_text = T - 35.  Unknown (or released) id: T3_E_NOTFOUND; a request submitted with alignment = 0 or a buffer too small:
  * T3_E_INVALID; not finished: T3_E_STATE. */
 int t3_get_alignment(T3Handle h, int64_t req_id, float* out, int32_t* n_frames, int32_t* n_text);
+/* Token time spans: WHEN each text token is spoken, from the matrices of n FINISHED, not yet released requests submitted with alignment >= 1,
+ * by one kernel launch (t3_align_path.hip, one wave per request); only the spans cross to the host.  The path is Glow-TTS's monotonic
+ * alignment search with a free end over integer cell scores (DESIGN.md section 8 states the contract):
+ *   w[k][t] = rint(1024 log2 a'), a' = A[k][t] clamped into [2^-64, 2^64] (NaN, zero and negatives: 2^-64), log2 by exponent + a degree-5 polynomial;
+ *   D[0][0] = w[0][0]; D[k][t] = w[k][t] + max(D[k-1][t], D[k-1][t-1]) for t <= k, the step from t - 1 taken only when strictly larger;
+ *   last = the lowest t with the largest D[n_frames-1][t]; the path runs back from (n_frames - 1, last) to (0, 0) in steps of 0 or 1.
+ * start / end: host arrays [n][ld]; row i holds, per text id t <= last[i], the first frame on t and one past its last frame, and -1 for every other
+ * t < ld (beyond last, beyond the request's n_text).  Seconds = frame / 25.  n_text, last, score (= D at the end cell): [n] each, nullable.
+ * ld smaller than some request's n_text: T3_E_INVALID; the other codes are t3_get_alignment's.  The call synchronises its own stream. */
+int t3_get_token_spans(T3Handle h, const int64_t* req_ids, int32_t n, int32_t ld, int32_t* start, int32_t* end, int32_t* n_text, int32_t* last,
+                       int32_t* score);
 
 /* ---- alignment guard: EOS suppressed or forced on the device, from the alignment frames --------------------------------
  * The logits half of upstream's AlignmentStreamAnalyzer, as a kernel inside the step (t3_guard.hip) and a sampler that obeys it.  For a request
@@ -367,6 +378,12 @@ int t3k_sample_ctl(const void* logits2_bf16, int32_t ldl, uint16_t* counts, cons
  * ctl_out [n_frames] = the control word of each frame, *final_state = the state behind the last one. */
 int t3k_alignment_guard(const float* A, int32_t n_frames, int32_t n_text, int32_t ld, const int32_t* tok, const T3GuardParams* params,
                         int32_t* ctl_out, T3GuardState* final_state);
+/* The path kernel of t3_get_token_spans on one host matrix A [n_frames][ld] (n_frames <= 8192, n_text <= 2112, ld >= n_text; the columns from n_text
+ * on are never read into a result): path [n_frames], start / end [n_text], *last, *score. */
+int t3k_align_path(const float* A, int32_t n_frames, int32_t n_text, int32_t ld, int32_t* path, int32_t* start, int32_t* end, int32_t* last,
+                   int32_t* score);
+/* Its cell score alone: w[i] = rint(1024 log2 a'[i]), |w| <= 65536. */
+int t3k_align_scores(const float* a, int32_t* w, int32_t n);
 /* The log-probability kernel (t3_logprobs.hip) for one utterance on host buffers: logits bf16 [2][ldl] as t3k_sample takes them (ldl a multiple of
  * 8), token = the drawn speech-space id, k in 0..T3_MAX_LOGPROBS.  top_ids (SPEECH-space) / top_lp [k], nullable when k = 0. */
 int t3k_logprobs(const void* logits2_bf16, int32_t ldl, float cfg, int32_t token, int32_t k, int32_t* rank, float* lp_tok,
