@@ -64,6 +64,8 @@ struct Request {
     int lp_k = -1;                    // t3_request_logprobs: top ids kept per token (-1 = not marked)
     int* d_lp = nullptr;              // finished, marked: its out.size() log-probability records of 2 (lp_K + 1) words, a pooled buffer of its own
     int lp_K = 0;                     // ... with the maximum of the reserve it ran under
+    std::vector<int32_t> proc_stage;  // t3_request_logit_processors: the staging image the build kernel reads at admission (empty = not marked)
+    int n_stop = 0, stops[PROC_MAX_STOP] = {-1, -1, -1, -1};      // ... and its stop list, sp.stop_token first; n_stop = 0: sp.stop_token alone
     double t_add = 0, t_admit = 0, t_first = 0, t_finish = 0;     // seconds since the engine was created (t3_get_timing)
 };
 
@@ -126,7 +128,7 @@ struct T3Engine {
         uint64_t waited_admit_seq = 0;     // the admission this group's stream has been ordered behind
         hipEvent_t ev_done[NBUF] = {};
         int rcap = 0;              // row budget per step
-        std::map<std::tuple<int, int, int, int, int>, hipGraphExec_t> graphs;   // (M, n_sel, first staging buffer, steps, tapped + 2 guarded + 4 logprobs) -> captured decode step(s)
+        std::map<std::tuple<int, int, int, int, int>, hipGraphExec_t> graphs;   // (M, n_sel, first staging buffer, steps, tapped + 2 guarded + 4 logprobs + 8 processors) -> captured decode step(s)
     };
     // One enqueued step: what the scheduler put on each group's stream, kept until its tokens are back.
     struct StepRec {
@@ -134,6 +136,7 @@ struct T3Engine {
         bool tapped = false;           // a sampled row of the step feeds the alignment export: the tap launches follow their layers' attention
         bool guarded = false;          // ... and one of them is guarded: the guard launch follows the last tap, the sampler obeys its control words
         bool logprobs = false;         // a sampled request of the step is marked (t3_request_logprobs): the log-probability launch follows the sampler
+        bool proc = false;             // a sampled request of the step is marked (t3_request_logit_processors): the sampler's third instantiation reads the records
         int max_prefill_ctx = 0;       // longest context among the step's prefill rows (sizes the tile attention's LDS)
         double sum_ctx = 0;
         std::vector<Request*> sampled;
@@ -182,6 +185,9 @@ struct T3Engine {
     // (-1 = the slot's request is not marked); lp_K < 0 = nothing reserved.  Finished requests keep their records in pooled buffers, as d_align does
     int *d_lp_rec = nullptr, *d_lp_k = nullptr; int lp_K = -1;
     std::vector<int*> lp_pool;         // free per-request record buffers of the current reserve (max_model_len x 2 (lp_K + 1) words each)
+    // logit processors (t3_reserve_logit_processors, t3_logitproc.hip): per slot a record of PROC_WORDS words the sampler reads, and PROC_STAGE_WORDS
+    // words of pinned host memory the request's lists wait in between admission and the build kernel; null = nothing reserved
+    uint32_t* d_proc = nullptr; int32_t* h_proc_stage = nullptr;
     std::deque<int64_t> finished_q;    // ids finished since the last t3_pop_finished (T3StepResult carries only the first 64 of a step)
     uint16_t* d_dbg_emb = nullptr;     // debug_logits: the embedded input rows of the most recent step (t3_debug_embeddings)
     std::vector<int> dbg_emb_rec;      // their (stream, position) pairs
@@ -296,6 +302,7 @@ extern "C" int t3_destroy(T3Handle e) {
     free_dev(e->d_align); free_dev(e->d_guard_state); free_dev(e->d_guard_ctl);
     for (float* b : e->align_pool) free_dev(b);
     free_dev(e->d_lp_rec); free_dev(e->d_lp_k);
+    free_dev(e->d_proc); if (e->h_proc_stage) (void)hipHostFree(e->h_proc_stage);
     for (int* b : e->lp_pool) free_dev(b);
     for (auto& kv : e->reqs) { free_dev(kv.second.d_align); free_dev(kv.second.d_lp); }
     if (e->ev_handoff) (void)hipEventDestroy(e->ev_handoff);
@@ -613,6 +620,13 @@ static int admit(T3Engine* e) {
         if (r.sp.alignment == 2) HIP_TRY(launch_guard_reset(e->d_guard_state, e->d_guard_ctl, slot, e->groups[slot % e->n_groups].stream));
         // a marked request's k word, there too: the previous occupant's word went back to -1 on that stream when it finished
         if (r.lp_k >= 0) HIP_TRY(launch_logprobs_mark(e->d_lp_k, slot, r.lp_k, e->groups[slot % e->n_groups].stream));
+        // a marked request's processor record, there too.  The slot's staging words are free: the build kernel of the previous occupant ran in front
+        // of the steps that had to complete before the slot could be released
+        if (!r.proc_stage.empty()) {
+            int32_t* stage = e->h_proc_stage + (size_t)slot * PROC_STAGE_WORDS;
+            memcpy(stage, r.proc_stage.data(), r.proc_stage.size() * 4);
+            HIP_TRY(launch_logitproc_build(stage, e->d_proc + (size_t)slot * PROC_WORDS, e->groups[slot % e->n_groups].stream));
+        }
         // r.cond / r.sp are kept alive in the request map until the copy is consumed (stream-ordered, pageable -> staged synchronously)
         e->running.push_back(r.id);
     }
@@ -733,6 +747,7 @@ static int launch_sample_phase(T3Engine* e, T3Engine::Group& g, const T3Engine::
     }
     { Prof p(e, K_SAMPLE, s); SampleArgs sa{g.logits, VPAD, g.dm.sel, e->d_counts, e->d_sp, e->cfg.cfg_scale, g.dm.out_tok, e->d_dbg, n_sel, e->d_hist, e->cfg.max_model_len, e->zero_copy ? g.h_out_tok[buf] : nullptr};
       if (sr.guarded) sa.eos_ctl = e->d_guard_ctl;
+      if (sr.proc) sa.proc = e->d_proc;
       HIP_TRY(launch_sampler(sa, s)); }
     if (sr.logprobs) {     // outside Prof: not a kernel class of its own.  Reads what the sampler has just left in out_tok and the head rows it read
         LogprobArgs la{g.logits, VPAD, g.dm.sel, g.dm.out_tok, e->d_lp_k, e->cfg.cfg_scale, e->d_lp_rec, e->cfg.max_model_len, e->lp_K, n_sel};
@@ -801,7 +816,7 @@ static int build_step(T3Engine* e, T3Engine::Step& st, bool may_admit) {
         hm.sel[sr.n_sel] = make_int4(r.slot, n, 0, 0);
         sr.sum_ctx += 2.0 * (pos + 1);
         r.last_idx = sr.n_sel; r.n_sched = n + 1;
-        sr.sampled.push_back(&r); ++sr.n_sel; sr.logprobs |= r.lp_k >= 0;
+        sr.sampled.push_back(&r); ++sr.n_sel; sr.logprobs |= r.lp_k >= 0; sr.proc |= !r.proc_stage.empty();
     }
     for (auto& sr : st.g) sr.decode_rows = sr.M;
     for (int64_t id : e->running) {
@@ -826,7 +841,7 @@ static int build_step(T3Engine* e, T3Engine::Step& st, bool may_admit) {
         if (p1 == T) {
             hm.sel[sr.n_sel] = make_int4(r.slot, 0, 0, 0);
             r.state = DECODE; r.n_sched = 1; r.last_idx = sr.n_sel;
-            sr.sampled.push_back(&r); ++sr.n_sel; sr.logprobs |= r.lp_k >= 0;
+            sr.sampled.push_back(&r); ++sr.n_sel; sr.logprobs |= r.lp_k >= 0; sr.proc |= !r.proc_stage.empty();
         }
     }
     for (auto& sr : st.g) { st.M_all += sr.M; st.n_prefill_rows += sr.n_prefill_rows; st.n_sampled += sr.n_sel; st.decode_rows += sr.decode_rows; st.sum_ctx += sr.sum_ctx; }
@@ -870,7 +885,7 @@ static int launch_steps(T3Engine* e, T3Engine::Step* steps, int n) {
             for (int r = 0; r < sr.M; ++r) { const int* rec = g.hm[buf].rows + (size_t)r * e->row_stride; e->dbg_emb_rec[2 * r] = rec[0]; e->dbg_emb_rec[2 * r + 1] = rec[1]; }
         }
         if (graphs_ok) {
-            const auto key = std::make_tuple(sr.M, sr.n_sel, e->zero_copy ? buf : 0, n, (int)sr.tapped + 2 * (int)sr.guarded + 4 * (int)sr.logprobs);      // zero-copy: the pinned buffers of `buf` ... are kernel arguments
+            const auto key = std::make_tuple(sr.M, sr.n_sel, e->zero_copy ? buf : 0, n, (int)sr.tapped + 2 * (int)sr.guarded + 4 * (int)sr.logprobs + 8 * (int)sr.proc);      // zero-copy: the pinned buffers of `buf` ... are kernel arguments
             auto it = g.graphs.find(key);
             if (it == g.graphs.end()) {
                 hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
@@ -974,7 +989,9 @@ static int complete_step(T3Engine* e, T3Engine::Step& st, T3StepResult* res, dou
             if (r.out.empty()) r.t_first = e->now_s();
             r.out.push_back(tok); e->st.tokens_generated++;
             int fin = 0;
-            if (!r.sp.ignore_eos && tok == r.sp.stop_token) fin = 1;
+            bool is_stop = tok == r.sp.stop_token;
+            for (int i = 0; i < r.n_stop; ++i) is_stop |= tok == r.stops[i];      // a marked request's list (t3_request_logit_processors)
+            if (!r.sp.ignore_eos && is_stop) fin = 1;
             else if ((int)r.out.size() >= r.limit) fin = 2;
             if (fin) {
                 r.state = FINISHED; r.finish_reason = fin; r.t_finish = e->now_s();
@@ -1028,6 +1045,10 @@ static int complete_step(T3Engine* e, T3Engine::Step& st, T3StepResult* res, dou
                     }
                     ce = launch_logprobs_mark(e->d_lp_k, r.slot, -1, e->groups[gi].stream);
                     if (ce != hipSuccess && !dev_rc) dev_rc = e->fail(T3_E_DEVICE, std::string("clearing a finished slot's log-probability mark failed: ") + hipGetErrorString(ce));
+                }
+                if (!r.proc_stage.empty()) {     // its processor record: unmarked, behind the steps already enqueued for it and ahead of the next occupant
+                    const hipError_t ce = launch_logitproc_reset(e->d_proc + (size_t)r.slot * PROC_WORDS, e->groups[gi].stream);
+                    if (ce != hipSuccess && !dev_rc) dev_rc = e->fail(T3_E_DEVICE, std::string("clearing a finished slot's logit-processor record failed: ") + hipGetErrorString(ce));
                 }
                 if (res->n_finished < 64) res->finished_ids[res->n_finished] = r.id;
                 res->n_finished++;
@@ -1384,6 +1405,43 @@ extern "C" int t3_get_logprobs(T3Handle e, int64_t req_id, float* lp_tok, int32_
     return T3_OK;
 }
 
+// ---- logit processors --------------------------------------------------------------------------------
+extern "C" int t3_reserve_logit_processors(T3Handle e, int32_t on) {
+    int rc;
+    if ((rc = check_ready(e))) return rc;
+    if (!e->running.empty() || !e->waiting.empty()) return e->fail(T3_E_STATE, "t3_reserve_logit_processors while requests are queued or running");
+    if ((rc = drop_graphs(e))) return rc;      // they carry the sampler's instantiation and the records' address
+    if (e->stream) HIP_TRY(hipStreamSynchronize(e->stream));
+    free_dev(e->d_proc); e->d_proc = nullptr;
+    if (e->h_proc_stage) { (void)hipHostFree(e->h_proc_stage); e->h_proc_stage = nullptr; }
+    if (!on) return T3_OK;
+    const size_t rec_bytes = (size_t)e->cfg.max_seqs * PROC_WORDS * 4, stage_bytes = (size_t)e->cfg.max_seqs * PROC_STAGE_WORDS * 4;
+    if (hipMalloc((void**)&e->d_proc, rec_bytes) != hipSuccess) {
+        e->d_proc = nullptr;
+        return e->fail(T3_E_NOMEM, "hipMalloc of " + std::to_string(rec_bytes) + " bytes for the logit-processor records failed");
+    }
+    if (hipHostMalloc((void**)&e->h_proc_stage, stage_bytes, hipHostMallocDefault) != hipSuccess) {
+        free_dev(e->d_proc); e->d_proc = nullptr; e->h_proc_stage = nullptr;
+        return e->fail(T3_E_NOMEM, "hipHostMalloc of " + std::to_string(stage_bytes) + " bytes for the logit-processor staging area failed");
+    }
+    memset(e->h_proc_stage, 0, stage_bytes);
+    HIP_TRY(hipMemset(e->d_proc, 0, rec_bytes));      // every slot: unmarked
+    return T3_OK;
+}
+
+extern "C" int t3_request_logit_processors(T3Handle e, int64_t req_id, const T3LogitProcessors* p) {
+    if (!e) return T3_E_INVALID;
+    auto it = e->reqs.find(req_id);
+    if (it == e->reqs.end()) return e->fail(T3_E_NOTFOUND, "unknown request id");
+    if (!e->d_proc) return e->fail(T3_E_STATE, "logit processors asked for before t3_reserve_logit_processors");
+    Request& r = it->second;
+    if (r.state != WAITING) return e->fail(T3_E_STATE, "request " + std::to_string(req_id) + " is already admitted");
+    if (const char* why = logitproc_check(p)) return e->fail(T3_E_INVALID, std::string("logit processors: ") + why);
+    r.proc_stage.assign((size_t)PROC_STAGE_ALLOW + (p->allowed_ids ? p->n_allowed : 0), 0);
+    r.n_stop = logitproc_stage(p, r.sp.stop_token, r.proc_stage.data(), r.stops);
+    return T3_OK;
+}
+
 // ---- alignment guard ---------------------------------------------------------------------------------
 extern "C" int t3_set_alignment_guard(T3Handle e, const T3GuardParams* params) {
     if (!e) return T3_E_INVALID;
@@ -1461,6 +1519,7 @@ extern "C" int t3_abort_request(T3Handle e, int64_t req_id) {
         for (auto& g : e->groups) if (g.stream) (void)hipStreamSynchronize(g.stream);      // nothing of it may still be running
         e->running.erase(std::remove(e->running.begin(), e->running.end(), req_id), e->running.end());
         if (r.lp_k >= 0 && r.slot >= 0 && e->d_lp_k) (void)launch_logprobs_mark(e->d_lp_k, r.slot, -1, e->groups[r.slot % e->n_groups].stream);
+        if (!r.proc_stage.empty() && r.slot >= 0 && e->d_proc) (void)launch_logitproc_reset(e->d_proc + (size_t)r.slot * PROC_WORDS, e->groups[r.slot % e->n_groups].stream);
         release_slot(e, r);
     }
     if (r.d_out) e->out_pool.push_back(r.d_out);

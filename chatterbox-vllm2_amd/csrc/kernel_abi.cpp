@@ -338,7 +338,7 @@ extern "C" int t3k_decode_attention_fp4(const void* ctx_qkv, int32_t n_content, 
 }
 
 static int sample_impl(const void* logits2, int32_t ldl, uint16_t* counts, const T3Sampling* sp, float cfg, uint32_t step,
-                       int32_t* token_out, float* logits_out, uint8_t* keep_out, int32_t ctl = -1);
+                       int32_t* token_out, float* logits_out, uint8_t* keep_out, int32_t ctl = -1, const T3LogitProcessors* lp = nullptr);
 extern "C" int t3k_sample(const void* logits2, int32_t ldl, uint16_t* counts, const T3Sampling* sp, float cfg, uint32_t step,
                           int32_t* token_out, float* logits_out) { return sample_impl(logits2, ldl, counts, sp, cfg, step, token_out, logits_out, nullptr); }
 /* t3k_sample + the SUPPORT of the draw: keep_out [8194] = 1 where the masks (penalties -> /T -> min-p -> top-k -> top-p) leave the id drawable */
@@ -353,8 +353,14 @@ extern "C" int t3k_sample_ctl(const void* logits2, int32_t ldl, uint16_t* counts
     if (ctl < GUARD_NONE || ctl > GUARD_FORCE || !sp || sp->stop_token < 0 || sp->stop_token >= V) return T3_E_INVALID;
     return sample_impl(logits2, ldl, counts, sp, cfg, step, token_out, logits_out, nullptr, ctl);
 }
+/* the sampler's third instantiation behind the build kernel: the record of slot 0 is made from *lp as the engine makes it at admission */
+extern "C" int t3k_sample_proc(const void* logits2, int32_t ldl, uint16_t* counts, const T3Sampling* sp, float cfg, uint32_t step,
+                               const T3LogitProcessors* lp, int32_t* token_out, float* logits_out, uint8_t* keep_out) {
+    if (logitproc_check(lp)) return T3_E_INVALID;
+    return sample_impl(logits2, ldl, counts, sp, cfg, step, token_out, logits_out, keep_out, -1, lp);
+}
 static int sample_impl(const void* logits2, int32_t ldl, uint16_t* counts, const T3Sampling* sp_in, float cfg, uint32_t step,
-                       int32_t* token_out, float* logits_out, uint8_t* keep_out, int32_t ctl) {
+                       int32_t* token_out, float* logits_out, uint8_t* keep_out, int32_t ctl, const T3LogitProcessors* lp) {
     if (!logits2 || !counts || !sp_in || !token_out || ldl < V) return T3_E_INVALID;
     T3Sampling sp_copy = *sp_in; const T3Sampling* sp = &sp_copy;
     if (ctl >= 0) sp_copy.alignment = 2;
@@ -370,13 +376,21 @@ static int sample_impl(const void* logits2, int32_t ldl, uint16_t* counts, const
     if (ctl >= 0) { K_TRY(dctl.from(&ctl, 4)); sa.eos_ctl = dctl.as<int>(); }
     DevBuf dkeep;
     if (keep_out) { K_TRY(dkeep.alloc(V, true)); sa.dbg_keep = dkeep.as<unsigned char>(); }
+    DevBuf dstage, drec, dproc;
+    if (lp) {
+        std::vector<int32_t> stage(PROC_STAGE_WORDS, 0); int32_t stops[PROC_MAX_STOP];
+        logitproc_stage(lp, sp->stop_token, stage.data(), stops);
+        K_TRY(dstage.from(stage.data(), stage.size() * 4)); K_TRY(drec.alloc((size_t)PROC_WORDS * 4, true)); K_TRY(dproc.alloc((size_t)V * 4, true));
+        K_TRY(launch_logitproc_build(dstage.as<int32_t>(), drec.as<uint32_t>(), nullptr));
+        sa.proc = drec.as<uint32_t>(); sa.dbg_proc = dproc.as<float>();
+    }
     K_TRY(launch_sampler(sa, nullptr));
     K_TRY(hipDeviceSynchronize());
     if (keep_out) K_TRY(hipMemcpy(keep_out, dkeep.p, V, hipMemcpyDeviceToHost));
     K_TRY(hipMemcpy(token_out, dtok.p, 4, hipMemcpyDeviceToHost));
     K_TRY(hipMemcpy(cpad.data(), dc.p, VPAD * 2, hipMemcpyDeviceToHost));
     memcpy(counts, cpad.data(), V * 2);
-    if (logits_out) K_TRY(hipMemcpy(logits_out, ddbg.p, (size_t)V * 4, hipMemcpyDeviceToHost));
+    if (logits_out) K_TRY(hipMemcpy(logits_out, lp ? dproc.p : ddbg.p, (size_t)V * 4, hipMemcpyDeviceToHost));
     return T3_OK;
 }
 

@@ -178,8 +178,31 @@ struct SampleArgs {
     unsigned char* dbg_keep = nullptr;   // nullable (parity hook t3k_sample_support): [max_seqs][V] 1 where the draw can return the id
     const int* eos_ctl = nullptr;  // nullable: [max_seqs] guard control words (t3_guard.hip), obeyed for the slots whose sp.alignment is 2.  Non-null
                                    // launches the sampler's guarded instantiation; null launches the kernel as it was before the guard existed
+    const uint32_t* proc = nullptr;    // nullable: [max_seqs][PROC_WORDS] logit-processor records (t3_logitproc.hip).  Non-null launches the sampler's third
+                                       // instantiation (it obeys eos_ctl too, where that is set); a slot whose record is unmarked is sampled as without it
+    float* dbg_proc = nullptr;         // nullable (parity hook t3k_sample_proc): [max_seqs][V] the logits behind the processors (allow, bias, min_tokens)
 };
 hipError_t launch_sampler(const SampleArgs& a, hipStream_t s);
+
+// Logit processors (t3_logitproc.hip; the contract stands in include/t3_engine.h, "logit processors").  A slot's RECORD, PROC_WORDS 32-bit words in
+// device memory, 16-byte aligned, is what the sampler reads:
+//   [0, 264)    allow bitmask: bit v & 31 of word v >> 5 set = id v may be drawn (bits from 8194 on are clear)
+//   [264, 328)  the biased ids, ascending, padded with INT32_MAX        [328, 392)  their fp32 biases, in the same order
+//   [392] 1 = marked, 0 = unmarked (nothing else of the record is valid then)   [393] min_tokens   [394] n_stop   [395] n_bias   [396, 400) the stop ids
+// The STAGING image of a request, PROC_STAGE_WORDS words in pinned host memory, is what the host writes and the build kernel reads:
+//   [0] n_allowed, -1 = every id   [1] n_bias   [2] min_tokens   [3] n_stop   [4, 8) stop ids   [8, 72) bias ids, any order   [72, 136) their biases
+//   [136, 136 + n_allowed) the allowed ids, any order, duplicates welcome
+constexpr int PROC_ALLOW_WORDS = 264, PROC_MAX_BIAS = T3_MAX_LOGIT_BIAS, PROC_MAX_STOP = 4;
+constexpr int PROC_IDS = PROC_ALLOW_WORDS, PROC_VALS = PROC_IDS + PROC_MAX_BIAS, PROC_HDR = PROC_VALS + PROC_MAX_BIAS, PROC_WORDS = PROC_HDR + 8;
+constexpr int PROC_STAGE_IDS = 8, PROC_STAGE_VALS = PROC_STAGE_IDS + PROC_MAX_BIAS, PROC_STAGE_ALLOW = PROC_STAGE_VALS + PROC_MAX_BIAS;
+constexpr int PROC_STAGE_WORDS = (PROC_STAGE_ALLOW + V + 3) & ~3;
+static_assert(PROC_ALLOW_WORDS * 32 >= VPAD && PROC_WORDS % 4 == 0 && PROC_MAX_BIAS == 64, "logit-processor record layout");
+// host: nullptr = well-formed, else what is malformed (t3_request_logit_processors' T3_E_INVALID cases); stop_token = T3Sampling.stop_token
+const char* logitproc_check(const T3LogitProcessors* p);
+// host: the staging image of a checked struct, PROC_STAGE_WORDS words; returns the request's stop list (stop_token first if it is one) in stops[4]
+int logitproc_stage(const T3LogitProcessors* p, int stop_token, int32_t* words, int32_t* stops);
+hipError_t launch_logitproc_build(const int32_t* stage, uint32_t* rec /*the slot's record*/, hipStream_t s);
+hipError_t launch_logitproc_reset(uint32_t* rec /*the slot's record*/, hipStream_t s);      // the record's flag word = 0, by a kernel
 
 // The alignment guard (t3_guard.hip): one wave per sampled utterance reads the frame the step's taps have just completed, moves the slot's
 // state (include/t3_engine.h spells the rules out) and leaves the control word the step's sampler obeys.

@@ -198,7 +198,34 @@ __device__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3
 // CTL: the guarded instantiation (SampleArgs.eos_ctl, t3_guard.hip).  A slot whose sp.alignment is 2 obeys its control word: GUARD_FORCE draws the
 // stop id whatever the logits hold (history and counts written as for any id), GUARD_SUPPRESS puts the stop id's post-CFG logit at -inf in front
 // of the penalties and everything behind them.  CTL = false compiles to the kernel as it was before the guard existed.
-template <bool CTL>
+//
+// PROC: the instantiation that runs a slot's logit processors (SampleArgs.proc, t3_logitproc.hip; contract: include/t3_engine.h).  PROC = false
+// compiles to the instructions the two instantiations had before it existed.  How the record reaches phase A:
+//   * allow mask: the eight ids of a thread's 16-byte vector are one BYTE of the mask, so the thread loads the one 32-bit word that holds it, beside
+//     its head-row loads (the tail lanes load the word of their single id): no load depends on another;
+//   * bias table: 64 sorted (id, fp32) pairs = 512 bytes.  The biases are added in phase A, in front of the penalties, i.e. BEFORE the first barrier
+//     of the kernel -- so the table is not shared through a barrier at all: every wave loads the table (one pair per lane, beside the logits) and
+//     keeps a copy of its own in LDS (PTAB words per wave), which only its own lanes read.  DS operations of one wave complete in order, so a
+//     wave-level fence is all that stands between the copy and its use, and no workgroup barrier is added;
+//   * a thread's ids are a run of eight: ONE branch-free lower bound over the sorted ids (6 LDS reads) finds the first pair of the run, and the run's
+//     pairs follow it; a run without any (nearly all of them: 64 pairs against 1024 runs) leaves after one compare;
+//   * min_tokens against the step index of the sampling record; the stop ids of a held step are folded into the thread's allow byte;
+//   * a slot whose record is unmarked skips all of it by a uniform branch (its loads of the record are issued and ignored).
+// A row that the processors leave without any finite logit draws the lowest id of its allow list (0 when that is empty).
+// PROC, a row without a finite logit: the lowest id of the allow list, 0 for an empty one.  allow8[k] = the allow byte of the thread's vector k,
+// tail_id = the tail lane's id if it is allowed, else -1.  Call with all threads (barriers inside).
+template <int KF_>
+__device__ __forceinline__ int proc_lowest_allowed(const uint32_t* allow8, int tail_id, int tid, unsigned long long* scr) {
+    uint32_t c = 0xffffffffu;
+#pragma unroll
+    for (int k = KF_ - 1; k >= 0; --k) if (allow8[k]) c = (uint32_t)((tid + STH * k) * 8 + __ffs((int)allow8[k]) - 1);
+    if (tail_id >= 0 && tail_id < V && (uint32_t)tail_id < c) c = (uint32_t)tail_id;
+    c = ~(uint32_t)block_max_u64((unsigned long long)(~c), scr);
+    return c < (uint32_t)V ? (int)c : 0;
+}
+constexpr int PTAB = PROC_MAX_BIAS + 8 + PROC_MAX_BIAS;      // per wave: [64] ids, [8] sentinels, [64] biases
+constexpr size_t PROC_LDS = (size_t)SWV * PTAB * 4;
+template <bool CTL, bool PROC>
 __global__ __launch_bounds__(STH) void sampler_kernel(SampleArgs a) {
 #ifdef T3_SAMPLER_CLK
     unsigned long long clk[12] = {0};
@@ -240,7 +267,7 @@ __global__ __launch_bounds__(STH) void sampler_kernel(SampleArgs a) {
 
     int suppress = -1;                                   // CTL: the id whose logit is -inf this step
     if constexpr (CTL) {
-        const int ctl = sp.alignment == 2 ? a.eos_ctl[slot] : GUARD_NONE;
+        const int ctl = (sp.alignment == 2 && (!PROC || a.eos_ctl)) ? a.eos_ctl[slot] : GUARD_NONE;
         if (ctl == GUARD_FORCE) { if (tid == 0) finish(sp.stop_token); return; }
         if (ctl == GUARD_SUPPRESS) suppress = sp.stop_token;
     }
@@ -255,28 +282,108 @@ __global__ __launch_bounds__(STH) void sampler_kernel(SampleArgs a) {
     constexpr int NVEC = VPAD / 8, KF = NVEC / STH, LV = NVEC - KF * STH, TAIL0 = KF * STH * 8;
     static_assert(VPAD % 8 == 0 && SLOTS >= VPAD && SLOTS % 2 == 0 && LV * 8 <= 64, "sampler vector layout");
     uint4 c4[KF], u4[KF], n4[KF];
+    // PROC: the record's header, the allow word of every vector, this lane's pair of the bias table
+    [[maybe_unused]] const uint32_t* prec = nullptr;
+    [[maybe_unused]] uint4 ph0 = make_uint4(0, 0, 0, 0), ph1 = ph0;
+    [[maybe_unused]] uint32_t aw[KF] = {}, awt = 0, tab_id = 0, tab_val = 0;
+    if constexpr (PROC) {
+        prec = a.proc + (size_t)slot * PROC_WORDS;
+        ph0 = reinterpret_cast<const uint4*>(prec + PROC_HDR)[0]; ph1 = reinterpret_cast<const uint4*>(prec + PROC_HDR)[1];
+        tab_id = prec[PROC_IDS + lane]; tab_val = prec[PROC_VALS + lane];
+    }
 #pragma unroll
     for (int k = 0; k < KF; ++k) {
         const int vi = tid + STH * k;
         c4[k] = reinterpret_cast<const uint4*>(lc)[vi];
         u4[k] = reinterpret_cast<const uint4*>(lu)[vi];
         n4[k] = reinterpret_cast<const uint4*>(counts)[vi];
+        if constexpr (PROC) aw[k] = prec[vi >> 2];       // ids 8 vi .. 8 vi + 7: byte vi & 3 of it
     }
     const bool tail = LV > 0 && wave == SWV - 1 && lane < LV * 8;
     uint16_t tc = 0, tu = 0, tn = 0;
-    if (tail) { tc = lc[TAIL0 + lane]; tu = lu[TAIL0 + lane]; tn = counts[TAIL0 + lane]; }
+    if (tail) {
+        tc = lc[TAIL0 + lane]; tu = lu[TAIL0 + lane]; tn = counts[TAIL0 + lane];
+        if constexpr (PROC) awt = prec[(TAIL0 + lane) >> 5];
+    }
     for (int v = VPAD + tid; v < SLOTS; v += STH) xs[v] = -INFINITY;
     constexpr int HC = 4, HSZ = HC * 64;                 // histogram copies (see the radix rounds), words per histogram
     unsigned long long* hmin = psum + 2 * HSZ;           // [2][HC][64] smallest / largest entry of a bin (rounds behind the octave round)
     unsigned long long* hmax = psum + 4 * HSZ;
     for (int j = tid; j < 2 * HSZ; j += STH) { psum[j] = 0; hmin[j] = ~0ull; hmax[j] = 0; }
     T3_CLK(1);
-    auto element = [&](uint16_t cb, uint16_t ub, uint32_t cnt, int v) -> float {
+    // PROC: what the processors do to this thread's ids, worked out from the record before the first logit is touched.  Per vector: the ids that stay
+    // (allow byte, less the stop ids while min_tokens holds them), the ids that carry a bias, and the biases; the same for the tail lane's one id
+    [[maybe_unused]] bool marked = false;
+    [[maybe_unused]] uint32_t allow8[KF] = {}, keep8[KF] = {}, bias8[KF] = {}, tallow = 0, tkeep = 0, tbias = 0;
+    [[maybe_unused]] float pb[KF][8] = {}, tb = 0.0f;
+    if constexpr (PROC) {
+        marked = ph0.x != 0u;
+        if (marked) {
+            uint32_t* tab = reinterpret_cast<uint32_t*>(psum + 6 * HSZ) + wave * PTAB;
+            const float* tabf = reinterpret_cast<const float*>(tab + PROC_MAX_BIAS + 8);
+            const int n_bias = (int)ph0.w, n_stop = (int)ph0.z < PROC_MAX_STOP ? (int)ph0.z : PROC_MAX_STOP;
+            const bool hold = step < ph0.y;                  // min_tokens: token `step` may not be a stop id yet
+            const int stops[PROC_MAX_STOP] = {(int)ph1.x, (int)ph1.y, (int)ph1.z, (int)ph1.w};
+            if (n_bias > 0) {
+                tab[lane] = tab_id; tab[PROC_MAX_BIAS + 8 + lane] = tab_val;
+                if (lane < 8) tab[PROC_MAX_BIAS + lane] = 0x7fffffffu;
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            }
+            auto lower_bound = [&](int key) -> int {         // pairs with an id below key, capped at 63: enough, since only an EQUAL id is ever used
+                int p = 0;
+#pragma unroll
+                for (int s = PROC_MAX_BIAS / 2; s >= 1; s >>= 1) p += ((int)tab[p + s - 1] < key) ? s : 0;
+                return p;
+            };
+#pragma unroll
+            for (int k = 0; k < KF; ++k) {
+                const int vi = tid + STH * k, base = vi * 8;
+                allow8[k] = (aw[k] >> ((vi & 3) * 8)) & 0xffu;
+                uint32_t keep = allow8[k];
+                if (hold) {
+#pragma unroll
+                    for (int s = 0; s < PROC_MAX_STOP; ++s) { const uint32_t d = (uint32_t)(stops[s] - base); if (s < n_stop && d < 8u) keep &= ~(1u << d); }
+                }
+                keep8[k] = keep;
+                if (n_bias > 0) {
+                    int p = lower_bound(base);
+                    int idp = (int)tab[p];
+                    if (idp < base + 8) {                        // the run holds a biased id (or p stopped at 63 below it: nothing will match)
+#pragma unroll
+                        for (int j = 0; j < 8; ++j)
+                            if (idp == base + j) { pb[k][j] = tabf[p]; bias8[k] |= 1u << j; ++p; idp = (int)tab[p]; }
+                    }
+                }
+            }
+            if (tail) {
+                const int v = TAIL0 + lane;
+                tallow = (awt >> (v & 31)) & 1u;
+                tkeep = tallow;
+                if (hold) {
+#pragma unroll
+                    for (int s = 0; s < PROC_MAX_STOP; ++s) if (s < n_stop && stops[s] == v) tkeep = 0u;
+                }
+                if (n_bias > 0) { const int p = lower_bound(v); if ((int)tab[p] == v) { tb = tabf[p]; tbias = 1u; } }
+            }
+        }
+    }
+    // pm (PROC): 1 = the processors leave the id at -inf, 2 = they add pb_ to it
+    auto element = [&](uint16_t cb, uint16_t ub, uint32_t cnt, int v, [[maybe_unused]] uint32_t pm, [[maybe_unused]] float pb_) -> float {
         float x = -INFINITY;
         if (v < V) {
             x = cfg_logit(cb, ub, a.cfg);
-            if constexpr (CTL) { if (v == suppress) x = -INFINITY; }
-            if (a.dbg) a.dbg[(size_t)slot * V + v] = x;
+            if constexpr (PROC) {
+                const bool sup = CTL && v == suppress;
+                if (a.dbg) a.dbg[(size_t)slot * V + v] = sup ? -INFINITY : x;      // what it held before the processors existed
+                if (pm & 1u) x = -INFINITY; else if (pm & 2u) x = x + pb_;
+                if (a.dbg_proc) a.dbg_proc[(size_t)slot * V + v] = x;
+                if (sup) x = -INFINITY;
+            } else {
+                if constexpr (CTL) { if (v == suppress) x = -INFINITY; }
+                if (a.dbg) a.dbg[(size_t)slot * V + v] = x;
+            }
             if (cnt > 0) {
                 if (sp.repetition_penalty != 1.0f) x = (x > 0.0f) ? x / sp.repetition_penalty : x * sp.repetition_penalty;
                 x = x - sp.frequency_penalty * (float)cnt;
@@ -303,13 +410,22 @@ __global__ __launch_bounds__(STH) void sampler_kernel(SampleArgs a) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int sh = (j & 1) * 16;
-            xs[vi * 8 + j] = element((uint16_t)(cw[j >> 1] >> sh), (uint16_t)(uw[j >> 1] >> sh), (nw[j >> 1] >> sh) & 0xFFFFu, vi * 8 + j);
+            uint32_t pm = 0;
+            if constexpr (PROC) pm = marked ? ((keep8[k] >> j) & 1u ? 0u : 1u) | ((bias8[k] >> j) & 1u ? 2u : 0u) : 0u;
+            xs[vi * 8 + j] = element((uint16_t)(cw[j >> 1] >> sh), (uint16_t)(uw[j >> 1] >> sh), (nw[j >> 1] >> sh) & 0xFFFFu, vi * 8 + j, pm, pb[k][j]);
         }
     }
-    if (tail) xs[TAIL0 + lane] = element(tc, tu, tn, TAIL0 + lane);
+    if (tail) xs[TAIL0 + lane] = element(tc, tu, tn, TAIL0 + lane, marked ? (tkeep ? 0u : 1u) | (tbias ? 2u : 0u) : 0u, tb);
     T3_CLK(2);
     if (greedy) {
         best = block_max_u64(best, scr);
+        if constexpr (PROC) {
+            if (marked && (uint32_t)(best >> 32) == 0x007fffffu) {      // the key of -inf
+                const int token = proc_lowest_allowed<KF>(allow8, tail && tallow ? TAIL0 + lane : -1, tid, scr);
+                if (tid == 0) { if (a.dbg_keep) a.dbg_keep[(size_t)slot * V + token] = 1; finish(token); }
+                return;
+            }
+        }
         if (tid == 0) {
             const int token = (int)(0xFFFFFFFFu - (uint32_t)best);
             if (a.dbg_keep) a.dbg_keep[(size_t)slot * V + (token < 0 ? 0 : (token >= V ? V - 1 : token))] = 1;      // (zeroed by the caller)
@@ -327,6 +443,13 @@ __global__ __launch_bounds__(STH) void sampler_kernel(SampleArgs a) {
         b = (uint32_t)waves_max_u64(s_mx, lane);
         b = (b & 0x80000000u) ? (b & 0x7fffffffu) : ~b;
         mx = __uint_as_float(b);
+    }
+    if constexpr (PROC) {
+        if (marked && mx == -INFINITY) {
+            const int token = proc_lowest_allowed<KF>(allow8, tail && tallow ? TAIL0 + lane : -1, tid, scr);
+            if (tid == 0) { if (a.dbg_keep) a.dbg_keep[(size_t)slot * V + token] = 1; finish(token); }
+            return;
+        }
     }
     // ---- weights.  From here on a thread owns SPT consecutive vocabulary entries and keeps them in registers (it reads their x from LDS:
     // the weights themselves never go through LDS).  floor(e x 2^32): e < 1 for all but the largest logits, and then the product is below
@@ -530,8 +653,9 @@ hipError_t prepare_kernels() {
     static bool done[MAX_DEVICES] = {};
     if (done[cur_device()]) return hipSuccess;
     const size_t lds = (size_t)(SLOTS / 2 + SSCR + 6 * 256) * sizeof(unsigned long long);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(sampler_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(sampler_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(sampler_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(sampler_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(sampler_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds + PROC_LDS));
     if (e == hipSuccess) e = prepare_gemm2();
     if (e == hipSuccess) done[cur_device()] = true;
     return e;
@@ -541,8 +665,9 @@ hipError_t launch_sampler(const SampleArgs& a, hipStream_t s) {
     const size_t lds = (size_t)(SLOTS / 2 + SSCR + 6 * 256) * sizeof(unsigned long long);
     hipError_t e = prepare_kernels();
     if (e != hipSuccess) return e;
-    if (a.eos_ctl) launch_k(sampler_kernel<true>, dim3(a.n), dim3(STH), lds, s, a);
-    else launch_k(sampler_kernel<false>, dim3(a.n), dim3(STH), lds, s, a);
+    if (a.proc) launch_k(sampler_kernel<true, true>, dim3(a.n), dim3(STH), lds + PROC_LDS, s, a);      // the bias table's per-wave copies behind the histograms
+    else if (a.eos_ctl) launch_k(sampler_kernel<true, false>, dim3(a.n), dim3(STH), lds, s, a);
+    else launch_k(sampler_kernel<false, false>, dim3(a.n), dim3(STH), lds, s, a);
     return hipGetLastError();
 }
 

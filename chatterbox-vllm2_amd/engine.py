@@ -92,6 +92,36 @@ class T3Stats(ct.Structure):
     ]
 
 
+class T3LogitProcessors(ct.Structure):
+    _fields_ = [("struct_size", ct.c_int32), ("n_allowed", ct.c_int32), ("allowed_ids", ct.c_void_p), ("bias_ids", ct.c_void_p),
+                ("bias_vals", ct.c_void_p), ("n_bias", ct.c_int32), ("min_tokens", ct.c_int32), ("extra_stop_ids", ct.c_int32 * 3),
+                ("n_extra_stop", ct.c_int32)]
+
+
+MAX_LOGIT_BIAS = 64     # T3_MAX_LOGIT_BIAS of include/t3_engine.h
+
+
+def make_logit_processors(allowed_ids=None, bias=None, min_tokens: int = 0, extra_stop_ids=()) -> T3LogitProcessors:
+    """The C struct of t3_request_logit_processors / t3k_sample_proc from SPEECH-space ids: allowed_ids an iterable or None (every id), bias a
+    {id: float} dict or a sequence of (id, float) pairs, kept in the given order.  Nothing is checked here: the library does that.  The struct keeps
+    the arrays it points at alive."""
+    lp = T3LogitProcessors()
+    lp.struct_size = ct.sizeof(T3LogitProcessors)
+    pairs = list(bias.items()) if isinstance(bias, dict) else list(bias or [])
+    lp._keep = (None if allowed_ids is None else np.ascontiguousarray(np.asarray(list(allowed_ids) + [0], dtype=np.int32)),
+                np.ascontiguousarray(np.asarray([p[0] for p in pairs] + [0], dtype=np.int32)),
+                np.ascontiguousarray(np.asarray([p[1] for p in pairs] + [0.0], dtype=np.float32)))
+    if lp._keep[0] is not None:
+        lp.allowed_ids = lp._keep[0].ctypes.data; lp.n_allowed = len(lp._keep[0]) - 1
+    lp.bias_ids = lp._keep[1].ctypes.data; lp.bias_vals = lp._keep[2].ctypes.data; lp.n_bias = len(pairs)
+    lp.min_tokens = int(min_tokens)
+    extra = [int(x) for x in extra_stop_ids]
+    lp.n_extra_stop = len(extra)
+    for i, x in enumerate(extra[:3]):
+        lp.extra_stop_ids[i] = x
+    return lp
+
+
 # every symbol include/t3_engine.h declares (tests/test_abi.py checks the library exports all of them)
 ABI_SYMBOLS = [
     "t3_create", "t3_destroy", "t3_last_error", "t3_load_tensor", "t3_finalize_weights", "t3_add_request",
@@ -103,6 +133,7 @@ ABI_SYMBOLS = [
     "t3_reserve_alignment", "t3_set_alignment_heads", "t3_get_alignment", "t3k_attention_probs",
     "t3_set_alignment_guard", "t3_get_guard", "t3k_alignment_guard", "t3k_sample_ctl",
     "t3_reserve_logprobs", "t3_request_logprobs", "t3_get_logprobs", "t3k_logprobs",
+    "t3_reserve_logit_processors", "t3_request_logit_processors", "t3k_sample_proc",
     "t3_get_token_spans", "t3k_align_path", "t3k_align_scores",
     "t3_cond_create", "t3_cond_destroy", "t3_cond_last_error", "t3_cond_load_tensor", "t3_cond_encode", "t3_cond_emotion_row",
     "t3k_ce_layernorm", "t3k_ce_linear", "t3k_ce_attention", "t3k_set_prefill_rows", "t3k_set_prefill_wide_rows",
@@ -188,6 +219,9 @@ def load_library():
     L.t3_request_logprobs.argtypes = [vp, i64, i32]
     L.t3_get_logprobs.argtypes = [vp, i64, vp, vp, vp, vp, ct.POINTER(i32), ct.POINTER(i32)]
     L.t3k_logprobs.argtypes = [vp, i32, ct.c_float, i32, i32, ct.POINTER(i32), ct.POINTER(ct.c_float), vp, vp]
+    L.t3_reserve_logit_processors.argtypes = [vp, i32]
+    L.t3_request_logit_processors.argtypes = [vp, i64, ct.POINTER(T3LogitProcessors)]
+    L.t3k_sample_proc.argtypes = [vp, i32, vp, ct.POINTER(T3Sampling), ct.c_float, ct.c_uint32, ct.POINTER(T3LogitProcessors), vp, vp, vp]
     L.t3_get_token_spans.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.t3k_align_path.argtypes = [vp, i32, i32, i32, vp, vp, vp, ct.POINTER(i32), ct.POINTER(i32)]
     L.t3k_align_scores.argtypes = [vp, vp, i32]
@@ -262,6 +296,7 @@ class T3Engine:
         self.alignment_max_text = 0       # text ids the alignment frames are reserved for (reserve_alignment)
         self.guard_params = None          # the enabled guard's parameters as a dict (set_alignment_guard), None = disabled
         self.logprobs_max_k = -1          # top ids per token the log-probability records are reserved for (reserve_logprobs), -1 = none
+        self.logit_processors_reserved = False      # reserve_logit_processors
         self.h = ct.c_void_p()
         rc = self.lib.t3_create(ct.byref(self.cfg), ct.byref(self.h))
         if rc:
@@ -434,6 +469,17 @@ class T3Engine:
         """Mark a request that is still waiting (after add_request, before the next step): keep the raw log-probability and rank of every id it
         draws and its k most likely ids (csrc/t3_logprobs.hip)."""
         self._chk(self.lib.t3_request_logprobs(self.h, int(req_id), int(k)))
+
+    def reserve_logit_processors(self, on: bool = True):
+        """Allocate (or free) the per-slot logit-processor records and their pinned staging area.  Only while nothing is queued or running."""
+        self.logit_processors_reserved = False
+        self._chk(self.lib.t3_reserve_logit_processors(self.h, int(bool(on))))
+        self.logit_processors_reserved = bool(on)
+
+    def request_logit_processors(self, req_id: int, lp: T3LogitProcessors):
+        """Mark a request that is still waiting (after add_request, before the next step) with the processors of make_logit_processors(): the
+        sampler kernel applies allow list, biases and min_tokens to its logits and every stop id of its list ends it (csrc/t3_logitproc.hip)."""
+        self._chk(self.lib.t3_request_logit_processors(self.h, int(req_id), ct.byref(lp)))
 
     def get_logprobs(self, req_id: int):
         """(lp_tok float32 [n], rank int32 [n], top_ids int32 [n, k] offset-space, top_lp float32 [n, k]) of a finished, unreleased, marked request."""
@@ -736,6 +782,18 @@ def k_sample_support(logits2: torch.Tensor, counts: torch.Tensor, sp: T3Sampling
     _chk_k(load_library().t3k_sample_support(logits2.data_ptr(), logits2.shape[1], counts.data_ptr(), ct.byref(sp), ct.c_float(cfg),
                                              ct.c_uint32(step), ct.byref(tok), keep.data_ptr()), "t3k_sample_support")
     return int(tok.value), keep.bool()
+
+
+def k_sample_proc(logits2: torch.Tensor, counts: torch.Tensor, sp: T3Sampling, cfg: float, step: int, lp: T3LogitProcessors):
+    """k_sample_support under logit processors at step index `step` -> (token, logits behind allow / bias / min_tokens [8194], keep [8194] bool)"""
+    logits2 = _bf(logits2)
+    assert counts.dtype == torch.uint16 and counts.numel() == C.SPEECH_VOCAB
+    tok = ct.c_int32(0)
+    lg = torch.empty(C.SPEECH_VOCAB, dtype=torch.float32)
+    keep = torch.zeros(C.SPEECH_VOCAB, dtype=torch.uint8)
+    _chk_k(load_library().t3k_sample_proc(logits2.data_ptr(), logits2.shape[1], counts.data_ptr(), ct.byref(sp), ct.c_float(cfg),
+                                          ct.c_uint32(step), ct.byref(lp), ct.addressof(tok), lg.data_ptr(), keep.data_ptr()), "t3k_sample_proc")
+    return int(tok.value), lg, keep.bool()
 
 
 def k_handoff(ids, text_token_count: int, flags: int = 1, ld: int = 0):

@@ -17,10 +17,11 @@ import warnings
 from dataclasses import dataclass, field
 from typing import Any, Dict, List, Optional, Sequence, Union
 
+import numpy as np
 import torch
 
 from . import constants as C
-from .engine import T3Engine, kv_cache_dtype_code, make_guard_params, make_sampling
+from .engine import MAX_LOGIT_BIAS, T3Engine, kv_cache_dtype_code, make_guard_params, make_logit_processors, make_sampling
 from .prompt import TextTokenizer, assemble_prompt_ids, find_tokenizer_file
 from .weights import iter_safetensors, synthetic_tensors
 
@@ -41,14 +42,16 @@ class SamplingParams:
     with vLLM's names and defaults.  Unknown keyword arguments are rejected like vLLM does."""
 
     _IGNORED = {"prompt_logprobs", "detokenize", "skip_special_tokens", "spaces_between_special_tokens",
-                "include_stop_str_in_output", "output_kind", "stop", "bad_words", "logit_bias", "allowed_token_ids",
-                "truncate_prompt_tokens", "guided_decoding", "extra_args", "min_tokens", "best_of", "logits_processors"}
+                "include_stop_str_in_output", "output_kind", "stop",
+                "truncate_prompt_tokens", "guided_decoding", "extra_args", "best_of", "logits_processors"}
 
     def __init__(self, n: int = 1, temperature: float = 1.0, top_p: float = 1.0, top_k: int = 0, min_p: float = 0.0,
                  repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
                  seed: Optional[int] = None, stop_token_ids: Optional[List[int]] = None, max_tokens: Optional[int] = 16,
                  ignore_eos: bool = False, pos_policy: int = 0, alignment: bool = False,
-                 alignment_guard: Union[bool, dict, None] = False, logprobs: Optional[int] = None, timestamps: bool = False, **kwargs):
+                 alignment_guard: Union[bool, dict, None] = False, logprobs: Optional[int] = None, timestamps: bool = False,
+                 logit_bias: Optional[Dict[int, float]] = None, allowed_token_ids: Optional[List[int]] = None,
+                 bad_words: Optional[list] = None, min_tokens: int = 0, **kwargs):
         for k, v in kwargs.items():
             if k not in self._IGNORED:
                 raise TypeError(f"SamplingParams got an unexpected keyword argument {k!r}")
@@ -72,6 +75,51 @@ class SamplingParams:
         self.repetition_penalty, self.presence_penalty, self.frequency_penalty = repetition_penalty, presence_penalty, frequency_penalty
         self.seed, self.stop_token_ids, self.max_tokens, self.ignore_eos = seed, list(stop_token_ids or []), max_tokens, ignore_eos
         self.pos_policy = pos_policy
+        # vLLM's logits processors, run inside the sampler kernel (csrc/t3_logitproc.hip; include/t3_engine.h "logit processors" has the order).
+        # Every id is in OFFSET space (speech id + 2500), as stop_token_ids and the output ids are.  logit_bias values are passed on as given:
+        # vLLM 0.10 clamps them to [-100, 100] only in SamplingParams.from_optional (its OpenAI server's path), not in the constructor this class
+        # stands for.  bad_words has no detokenizer to go through here: an entry is one offset-space id, bare or as a list of one, and becomes a
+        # bias of -inf.  At most 64 ids may carry a bias, bad_words included, and at most 4 stop ids end a request.
+        lo, hi = C.SPEECH_TOKEN_OFFSET, C.SPEECH_TOKEN_OFFSET + C.SPEECH_VOCAB
+
+        def speech_id(v, what):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"{what}: {v!r} is not a token id")
+            if not lo <= int(v) < hi:
+                raise ValueError(f"{what}: id {v} is outside the speech range [{lo}, {hi}) -- ids at this surface carry the +{lo} offset")
+            return int(v) - lo
+
+        self.logit_bias, self.allowed_token_ids, self.bad_words, self.min_tokens = logit_bias, allowed_token_ids, bad_words, int(min_tokens)
+        bias = {}
+        for k, v in (logit_bias or {}).items():
+            v = float(v)
+            if v != v or v == float("inf"):
+                raise ValueError(f"logit_bias[{k}] = {v}: a bias must be finite or -inf")
+            bias[speech_id(k, "logit_bias")] = v
+        for w in bad_words or []:
+            if isinstance(w, (list, tuple)):
+                if len(w) != 1:
+                    raise ValueError(f"bad_words entry {w!r}: only single-token entries are supported (there is no detokenizer on the T3 path)")
+                w = w[0]
+            if isinstance(w, str):
+                raise ValueError(f"bad_words entry {w!r}: give the offset-space token id, there is no detokenizer on the T3 path")
+            bias[speech_id(w, "bad_words")] = float("-inf")
+        if len(bias) > MAX_LOGIT_BIAS:
+            raise ValueError(f"{len(bias)} biased ids (logit_bias and bad_words together): at most {MAX_LOGIT_BIAS}")
+        if allowed_token_ids is not None and len(allowed_token_ids) == 0:
+            raise ValueError("allowed_token_ids must not be empty")
+        allowed = None if allowed_token_ids is None else sorted({speech_id(v, "allowed_token_ids") for v in allowed_token_ids})
+        if self.min_tokens < 0:
+            raise ValueError(f"min_tokens must be non-negative, got {min_tokens}")
+        if max_tokens is not None and self.min_tokens > max_tokens:
+            raise ValueError(f"min_tokens must be at most max_tokens = {max_tokens}, got {min_tokens}")
+        if len(self.stop_token_ids) > 4:
+            raise ValueError(f"at most 4 stop_token_ids, got {len(self.stop_token_ids)}")
+        stops = [speech_id(v, "stop_token_ids") for v in self.stop_token_ids]
+        # what LLM.generate marks the request with (speech-space), None when there is nothing to do
+        self.processors = None
+        if bias or allowed is not None or self.min_tokens > 0 or len(stops) > 1:
+            self.processors = dict(allowed_ids=allowed, bias=bias, min_tokens=self.min_tokens, extra_stop_ids=stops[1:])
         # vLLM's logprobs: None = off; k in 0..20 = the log-probability and rank of every drawn id plus the k most likely ids per token
         # (CompletionOutput.logprobs / cumulative_logprob), from a kernel behind the sampler (csrc/t3_logprobs.hip).  Only vLLM's default mode is
         # built: RAW log-probabilities of the post-CFG logits -- penalties, temperature, top-k / top-p / min-p and the alignment guard's suppression
@@ -322,12 +370,12 @@ class LLM:
         asked = [sp.logprobs for sp in sps if sp.logprobs is not None]
         if asked and max(asked) > self.engine.logprobs_max_k:
             self.engine.reserve_logprobs(max(asked))         # once for the call's largest k, before anything of it is queued
+        if any(sp.processors for sp in sps) and not self.engine.logit_processors_reserved:
+            self.engine.reserve_logit_processors(True)       # on first use, before anything of the call is queued
         for i, ((text, tids, cond), sp) in enumerate(zip(texts, sps)):
             final = assemble_prompt_ids(tids)
             stop = -1
-            if sp.stop_token_ids:
-                if len(sp.stop_token_ids) > 1:
-                    raise ValueError("the T3 engine supports one stop token id")
+            if sp.stop_token_ids:       # the first is T3Sampling.stop_token (the guard's), the others ride in the request's processors
                 stop = int(sp.stop_token_ids[0]) - C.SPEECH_TOKEN_OFFSET          # 9062 -> 6562 (tts.py:458)
             max_tokens = sp.max_tokens if sp.max_tokens is not None else self.max_model_len
             if sp.seed is not None:
@@ -346,6 +394,8 @@ class LLM:
             queued.append(rid)
             if sp.logprobs is not None:
                 self.engine.request_logprobs(rid, sp.logprobs)
+            if sp.processors:
+                self.engine.request_logit_processors(rid, make_logit_processors(**sp.processors))
             metas.append((rid, text, final, sp.alignment, sp.alignment_guard is not None, sp.logprobs is not None, sp.timestamps))
 
     def shutdown(self):

@@ -274,6 +274,44 @@ int t3_request_logprobs(T3Handle h, int64_t req_id, int32_t k);
  * own).  Error codes as t3_get_alignment. */
 int t3_get_logprobs(T3Handle h, int64_t req_id, float* lp_tok, int32_t* rank, int32_t* top_ids, float* top_lp, int32_t* n_tokens, int32_t* k);
 
+/* ---- logit processors -------------------------------------------------------------------------------------------------------
+ * vLLM's SamplingParams(allowed_token_ids=, logit_bias=, bad_words= (single ids), min_tokens=, stop_token_ids=) inside the sampler kernel: the
+ * post-CFG logits exist on the device only, for one step, and a burst replays four steps with no host in between.  For a marked request at step k
+ * (the step that draws token k), x_v = the post-CFG fp32 logit as the sampler forms it (cfg_logit).  In this order, in front of the guard's
+ * suppression, the penalties, temperature, min-p, top-k and top-p:
+ *   1. allowed_ids given and v not among them:  x_v = -inf;
+ *   2. x_v = x_v + b_v for every (v, b_v) of the bias list: ONE fp32 add per listed id, none for the others.  b_v = -inf is allowed (bad_words);
+ *   3. k < min_tokens:  x_s = -inf for every stop id s of the request;
+ *   4. the guard's SUPPRESS applies as before; its FORCE draws T3Sampling.stop_token whatever the logits hold.
+ * vLLM is not part of the reference tree: like the sampler's masks, this order is this project's restatement of vLLM 0.10's (allowed ids and bias
+ * and min_tokens are its logits processors, which run in front of its penalties) and is not pinned by the reference.
+ * Stop ids: T3Sampling.stop_token (when >= 0) and up to 3 extra ones.  The request finishes with reason 1 when it draws ANY of them; the guard forces
+ * and suppresses the first only.  Raw log-probabilities, t3_debug_logits and the alignment export are defined in front of steps 1-3 and do not change.
+ * A row whose every id ends at -inf draws the lowest id of the allow list (the lowest id, 0, without a list; id 0 too when the list is empty),
+ * sampled or greedy alike; NaN decides nothing.
+ * A step that samples no marked request launches exactly what it launches without the feature; an unmarked request's ids do not depend on it, and a
+ * marked request's ids are bit-identical between eager steps, captured graphs, bursts and batch compositions. */
+#define T3_MAX_LOGIT_BIAS 64
+typedef struct {
+    int32_t struct_size;           /* sizeof(T3LogitProcessors) */
+    int32_t n_allowed;             /* 0..8194 entries of allowed_ids (ignored when that is NULL) */
+    const int32_t* allowed_ids;    /* SPEECH-space, any order, duplicates allowed; NULL = every id */
+    const int32_t* bias_ids;       /* SPEECH-space, any order, no duplicates */
+    const float* bias_vals;        /* finite or -inf */
+    int32_t n_bias;                /* 0..T3_MAX_LOGIT_BIAS */
+    int32_t min_tokens;            /* >= 0 */
+    int32_t extra_stop_ids[3];     /* SPEECH-space */
+    int32_t n_extra_stop;          /* 0..3 */
+} T3LogitProcessors;
+/* on != 0 allocates the per-slot records (1600 bytes each) and the pinned staging area, 0 frees them.  Valid only while nothing is queued or
+ * running (T3_E_STATE).  Drops the captured step graphs. */
+int t3_reserve_logit_processors(T3Handle h, int32_t on);
+/* Marks a request that is still waiting (between t3_add_request and the next step call).  Unknown id: T3_E_NOTFOUND; before a reserve, or once the
+ * request is admitted: T3_E_STATE; T3_E_INVALID for a wrong struct_size, an id outside [0, 8194), n_allowed outside [0, 8194], n_bias outside
+ * [0, 64], a bias id listed twice, a bias that is NaN or +inf, min_tokens < 0 or n_extra_stop outside [0, 3].  What is well-formed is accepted: a
+ * stop id outside the allow list, or a min_tokens beyond max_tokens, only means that the request ends at its length limit. */
+int t3_request_logit_processors(T3Handle h, int64_t req_id, const T3LogitProcessors* p);
+
 /* ---- parity / measurement hooks --------------------------------------------------------- */
 /* post-CFG logits [8194] (speech-space, before the 2500-wide -inf pad of t3.py:669-672) of the
  * most recent sampled step of req_id; needs cfg.debug_logits = 1. */
@@ -373,6 +411,11 @@ int t3k_expf(const float* x, float* y, int32_t n);
 /* t3k_sample under a guard control word (0 nothing, 1 suppress sp->stop_token, 2 force it): the sampler's guarded instantiation. */
 int t3k_sample_ctl(const void* logits2_bf16, int32_t ldl, uint16_t* counts, const T3Sampling* sp, float cfg,
                    uint32_t step, int32_t ctl, int32_t* token_out, float* logits_out_8194 /*nullable*/);
+/* t3k_sample_support under logit processors: the build kernel makes the record from *lp (checked as t3_request_logit_processors checks it), then the
+ * sampler's third instantiation draws token `step` (the k of the contract).  logits_out_8194 (nullable) = the logits behind step 3 of the contract,
+ * in front of the penalties; keep_out_8194 (nullable) = the support of the draw. */
+int t3k_sample_proc(const void* logits2_bf16, int32_t ldl, uint16_t* counts, const T3Sampling* sp, float cfg, uint32_t step,
+                    const T3LogitProcessors* lp, int32_t* token_out, float* logits_out_8194, uint8_t* keep_out_8194);
 /* The guard kernel (t3_guard.hip) over a host matrix A [n_frames][ld] (ld a multiple of 4, >= n_text; the columns from n_text on are never read
  * into a result) and the ids tok [n_frames] drawn at each frame: one launch per frame in frame order, as the engine's steps do it.
  * ctl_out [n_frames] = the control word of each frame, *final_state = the state behind the last one. */
