@@ -184,6 +184,7 @@ struct T3Engine {
     // per-token log-probabilities (t3_reserve_logprobs, t3_logprobs.hip): per slot [max_model_len steps][2 (lp_K + 1)] record words and one k word
     // (-1 = the slot's request is not marked); lp_K < 0 = nothing reserved.  Finished requests keep their records in pooled buffers, as d_align does
     int *d_lp_rec = nullptr, *d_lp_k = nullptr; int lp_K = -1;
+    int lp_mode = 0;                   // t3_set_logprobs_mode: 0 raw, 1 processed -- which instantiation of the log-probability kernel a marked step launches
     std::vector<int*> lp_pool;         // free per-request record buffers of the current reserve (max_model_len x 2 (lp_K + 1) words each)
     // logit processors (t3_reserve_logit_processors, t3_logitproc.hip): per slot a record of PROC_WORDS words the sampler reads, and PROC_STAGE_WORDS
     // words of pinned host memory the request's lists wait in between admission and the build kernel; null = nothing reserved
@@ -751,6 +752,11 @@ static int launch_sample_phase(T3Engine* e, T3Engine::Group& g, const T3Engine::
       HIP_TRY(launch_sampler(sa, s)); }
     if (sr.logprobs) {     // outside Prof: not a kernel class of its own.  Reads what the sampler has just left in out_tok and the head rows it read
         LogprobArgs la{g.logits, VPAD, g.dm.sel, g.dm.out_tok, e->d_lp_k, e->cfg.cfg_scale, e->d_lp_rec, e->cfg.max_model_len, e->lp_K, n_sel};
+        if (e->lp_mode == 1) {     // processed: over what the sampler above drew from, so it is handed exactly what that launch was handed
+            la.counts = e->d_counts; la.sp = e->d_sp; la.mode = 1;
+            if (sr.guarded) la.eos_ctl = e->d_guard_ctl;
+            if (sr.proc) la.proc = e->d_proc;
+        }
         HIP_TRY(launch_logprobs(la, s));
     }
     return T3_OK;
@@ -1361,6 +1367,17 @@ extern "C" int t3_reserve_logprobs(T3Handle e, int32_t max_k) {
     }
     HIP_TRY(hipMemset(e->d_lp_k, 0xff, (size_t)e->cfg.max_seqs * 4));      // every slot: -1, not marked
     e->lp_K = max_k;
+    return T3_OK;
+}
+
+extern "C" int t3_set_logprobs_mode(T3Handle e, int32_t mode) {
+    if (!e) return T3_E_INVALID;
+    if (mode != 0 && mode != 1) return e->fail(T3_E_INVALID, "logprobs mode " + std::to_string(mode) + ": 0 (raw) or 1 (processed)");
+    if (!e->running.empty() || !e->waiting.empty()) return e->fail(T3_E_STATE, "t3_set_logprobs_mode while requests are queued or running");
+    (void)hipSetDevice(e->cfg.device_id);
+    int rc;
+    if ((rc = drop_graphs(e))) return rc;      // they carry the instantiation and its arguments
+    e->lp_mode = mode;
     return T3_OK;
 }
 

@@ -414,6 +414,46 @@ extern "C" int t3k_logprobs(const void* logits2, int32_t ldl, float cfg, int32_t
     return T3_OK;
 }
 
+/* its processed instantiation for one utterance: slot 0, token `step`.  counts = what the step's sampler USED; the device copy gets the drawn id's
+ * increment as sampler_kernel's finish() leaves it, because that is the state the kernel meets in the engine.  The record of *lp is built as at
+ * admission; ctl >= 0 marks the slot guarded in the kernel's copy of sp, as t3k_sample_ctl does. */
+extern "C" int t3k_logprobs_processed(const void* logits2, int32_t ldl, float cfg, const uint16_t* counts, const T3Sampling* sp_in, const T3LogitProcessors* lp,
+                                      int32_t ctl, uint32_t step, int32_t token, int32_t k, int32_t* rank, float* lp_tok, int32_t* top_ids, float* top_lp) {
+    if (!logits2 || !counts || !sp_in || !rank || !lp_tok || ldl < V || (ldl & 7) || token < 0 || token >= V || k < 0 || k > T3_MAX_LOGPROBS ||
+        (k > 0 && (!top_ids || !top_lp)) || ctl < -1 || ctl > GUARD_FORCE || step >= 8192u /* the engine's largest max_model_len */)
+        return T3_E_INVALID;
+    if (ctl >= 0 && (sp_in->stop_token < 0 || sp_in->stop_token >= V)) return T3_E_INVALID;
+    if (lp && logitproc_check(lp)) return T3_E_INVALID;
+    if (!have_device()) return T3_E_DEVICE;
+    T3Sampling sp = *sp_in;
+    if (ctl >= 0) sp.alignment = 2;
+    std::vector<uint16_t> cpad(VPAD, 0);
+    memcpy(cpad.data(), counts, V * 2);
+    if (cpad[token] < 65535) ++cpad[token];
+    const int4 sel = make_int4(0, (int)step, 0, 0);
+    const size_t recw = (size_t)2 * (k + 1);      // the kernel writes record `step` of step + 1
+    std::vector<int32_t> rec(recw, 0);
+    DevBuf dl, dc, dsp, dsel, dtok, dk, drec, dctl, dstage, dproc;
+    K_TRY(dl.from(logits2, (size_t)2 * ldl * 2)); K_TRY(dc.from(cpad.data(), VPAD * 2)); K_TRY(dsp.from(&sp, sizeof(sp)));
+    K_TRY(dsel.from(&sel, sizeof(sel))); K_TRY(dtok.from(&token, 4)); K_TRY(dk.from(&k, 4)); K_TRY(drec.alloc((size_t)(step + 1) * recw * 4, true));
+    LogprobArgs la{dl.as<uint16_t>(), ldl, dsel.as<int4>(), dtok.as<int>(), dk.as<int>(), cfg, drec.as<int>(), (int)step + 1, k, 1};
+    la.counts = dc.as<uint16_t>(); la.sp = dsp.as<T3Sampling>(); la.mode = 1;
+    if (ctl >= 0) { K_TRY(dctl.from(&ctl, 4)); la.eos_ctl = dctl.as<int>(); }
+    if (lp) {
+        std::vector<int32_t> stage(PROC_STAGE_WORDS, 0); int32_t stops[PROC_MAX_STOP];
+        logitproc_stage(lp, sp.stop_token, stage.data(), stops);
+        K_TRY(dstage.from(stage.data(), stage.size() * 4)); K_TRY(dproc.alloc((size_t)PROC_WORDS * 4, true));
+        K_TRY(launch_logitproc_build(dstage.as<int32_t>(), dproc.as<uint32_t>(), nullptr));
+        la.proc = dproc.as<uint32_t>();
+    }
+    K_TRY(launch_logprobs(la, nullptr));
+    K_TRY(hipDeviceSynchronize());
+    K_TRY(hipMemcpy(rec.data(), drec.as<int>() + (size_t)step * recw, recw * 4, hipMemcpyDeviceToHost));
+    *rank = rec[0]; memcpy(lp_tok, &rec[1], 4);
+    for (int i = 0; i < k; ++i) { top_ids[i] = rec[2 + 2 * i]; memcpy(top_lp + i, &rec[3 + 2 * i], 4); }
+    return T3_OK;
+}
+
 /* the hand-off kernel on host buffers: ids [n] speech-space -> out [ld] (padded with 0), *len */
 extern "C" int t3k_handoff(const int32_t* ids, int32_t n, int32_t text_token_count, int32_t flags, int32_t* out, int32_t ld, int32_t* len) {
     if ((!ids && n > 0) || !out || !len || n < 0 || ld <= 0) return T3_E_INVALID;

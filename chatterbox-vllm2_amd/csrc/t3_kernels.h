@@ -236,6 +236,14 @@ struct LogprobArgs {
     int* rec;                  // [max_seqs][rec_steps][2 (K + 1)] 32-bit words
     int rec_steps, K;
     int n;
+    // mode 1 = PROCESSED (t3_set_logprobs_mode): over z_v, the value the sampler draws from -- behind the slot's logit processors, the guard's
+    // suppression, the penalties and the temperature.  It reads what the step's sampler read: counts / sp as SampleArgs has them (the drawn id's count
+    // already raised), proc / eos_ctl nullable exactly where the sampler's launch left them null.  mode 0 reads none of the five.
+    const uint16_t* counts = nullptr;      // [max_seqs][VPAD], 16-byte aligned
+    const T3Sampling* sp = nullptr;        // [max_seqs]
+    const uint32_t* proc = nullptr;        // nullable: [max_seqs][PROC_WORDS]
+    const int* eos_ctl = nullptr;          // nullable: [max_seqs]
+    int mode = 0;
 };
 hipError_t launch_logprobs(const LogprobArgs& a, hipStream_t s);
 hipError_t launch_logprobs_mark(int* lp_k, int slot, int k, hipStream_t s);     // lp_k[slot] = k, by a kernel

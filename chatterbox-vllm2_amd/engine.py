@@ -122,6 +122,9 @@ def make_logit_processors(allowed_ids=None, bias=None, min_tokens: int = 0, extr
     return lp
 
 
+# vLLM's logprobs_mode strings -> t3_set_logprobs_mode; its two *_logits modes are not built
+LOGPROBS_MODES = {"raw_logprobs": 0, "processed_logprobs": 1}
+
 # every symbol include/t3_engine.h declares (tests/test_abi.py checks the library exports all of them)
 ABI_SYMBOLS = [
     "t3_create", "t3_destroy", "t3_last_error", "t3_load_tensor", "t3_finalize_weights", "t3_add_request",
@@ -132,7 +135,7 @@ ABI_SYMBOLS = [
     "t3k_fp4_roundtrip", "t3k_rope_attention_fp4", "t3k_decode_attention_fp4",
     "t3_reserve_alignment", "t3_set_alignment_heads", "t3_get_alignment", "t3k_attention_probs",
     "t3_set_alignment_guard", "t3_get_guard", "t3k_alignment_guard", "t3k_sample_ctl",
-    "t3_reserve_logprobs", "t3_request_logprobs", "t3_get_logprobs", "t3k_logprobs",
+    "t3_reserve_logprobs", "t3_request_logprobs", "t3_get_logprobs", "t3k_logprobs", "t3_set_logprobs_mode", "t3k_logprobs_processed",
     "t3_reserve_logit_processors", "t3_request_logit_processors", "t3k_sample_proc",
     "t3_get_token_spans", "t3k_align_path", "t3k_align_scores",
     "t3_cond_create", "t3_cond_destroy", "t3_cond_last_error", "t3_cond_load_tensor", "t3_cond_encode", "t3_cond_emotion_row",
@@ -219,6 +222,9 @@ def load_library():
     L.t3_request_logprobs.argtypes = [vp, i64, i32]
     L.t3_get_logprobs.argtypes = [vp, i64, vp, vp, vp, vp, ct.POINTER(i32), ct.POINTER(i32)]
     L.t3k_logprobs.argtypes = [vp, i32, ct.c_float, i32, i32, ct.POINTER(i32), ct.POINTER(ct.c_float), vp, vp]
+    L.t3_set_logprobs_mode.argtypes = [vp, i32]
+    L.t3k_logprobs_processed.argtypes = [vp, i32, ct.c_float, vp, ct.POINTER(T3Sampling), ct.POINTER(T3LogitProcessors), i32, ct.c_uint32, i32, i32,
+                                         ct.POINTER(i32), ct.POINTER(ct.c_float), vp, vp]
     L.t3_reserve_logit_processors.argtypes = [vp, i32]
     L.t3_request_logit_processors.argtypes = [vp, i64, ct.POINTER(T3LogitProcessors)]
     L.t3k_sample_proc.argtypes = [vp, i32, vp, ct.POINTER(T3Sampling), ct.c_float, ct.c_uint32, ct.POINTER(T3LogitProcessors), vp, vp, vp]
@@ -297,6 +303,7 @@ class T3Engine:
         self.guard_params = None          # the enabled guard's parameters as a dict (set_alignment_guard), None = disabled
         self.logprobs_max_k = -1          # top ids per token the log-probability records are reserved for (reserve_logprobs), -1 = none
         self.logit_processors_reserved = False      # reserve_logit_processors
+        self.logprobs_mode = "raw_logprobs"         # set_logprobs_mode
         self.h = ct.c_void_p()
         rc = self.lib.t3_create(ct.byref(self.cfg), ct.byref(self.h))
         if rc:
@@ -469,6 +476,14 @@ class T3Engine:
         """Mark a request that is still waiting (after add_request, before the next step): keep the raw log-probability and rank of every id it
         draws and its k most likely ids (csrc/t3_logprobs.hip)."""
         self._chk(self.lib.t3_request_logprobs(self.h, int(req_id), int(k)))
+
+    def set_logprobs_mode(self, mode: str):
+        """'raw_logprobs' (the default: over the post-CFG logits) or 'processed_logprobs' (over what the sampler draws from: behind the logit
+        processors, the guard's suppression, the penalties and the temperature; include/t3_engine.h).  Only while nothing is queued or running."""
+        if mode not in LOGPROBS_MODES:
+            raise ValueError(f"logprobs_mode {mode!r}: the T3 engine builds {sorted(LOGPROBS_MODES)}")
+        self._chk(self.lib.t3_set_logprobs_mode(self.h, LOGPROBS_MODES[mode]))
+        self.logprobs_mode = mode
 
     def reserve_logit_processors(self, on: bool = True):
         """Allocate (or free) the per-slot logit-processor records and their pinned staging area.  Only while nothing is queued or running."""
@@ -699,6 +714,20 @@ def k_logprobs(logits2: torch.Tensor, cfg: float, token: int, k: int):
     _chk_k(load_library().t3k_logprobs(logits2.data_ptr(), logits2.shape[1], ct.c_float(cfg), int(token), int(k), ct.byref(rank), ct.byref(lp),
                                        ids.ctypes.data, tlp.ctypes.data), "t3k_logprobs")
     return int(rank.value), float(lp.value), ids[:k], tlp[:k]
+
+
+def k_logprobs_processed(logits2: torch.Tensor, cfg: float, counts: torch.Tensor, sp: T3Sampling, token: int, k: int, step: int = 0, ctl: int = -1,
+                         lp: Optional[T3LogitProcessors] = None):
+    """The log-probability kernel's processed instantiation: counts uint16 [8194] as the step's sampler used them, lp = make_logit_processors(...)
+    or None, ctl = -1 (no control word) or the guard's 0 / 1 / 2 -> (rank, lp_tok, top_ids int32 [k] speech-space, top_lp float32 [k])."""
+    logits2 = _bf(logits2)
+    assert counts.dtype == torch.uint16 and counts.numel() == C.SPEECH_VOCAB
+    rank = ct.c_int32(0); lpt = ct.c_float(0)
+    ids = np.zeros(max(1, k), dtype=np.int32); tlp = np.zeros(max(1, k), dtype=np.float32)
+    _chk_k(load_library().t3k_logprobs_processed(logits2.data_ptr(), logits2.shape[1], ct.c_float(cfg), counts.data_ptr(), ct.byref(sp),
+                                                 ct.byref(lp) if lp is not None else None, int(ctl), ct.c_uint32(step), int(token), int(k),
+                                                 ct.byref(rank), ct.byref(lpt), ids.ctypes.data, tlp.ctypes.data), "t3k_logprobs_processed")
+    return int(rank.value), float(lpt.value), ids[:k], tlp[:k]
 
 
 def k_fp8_roundtrip(x: torch.Tensor) -> torch.Tensor:

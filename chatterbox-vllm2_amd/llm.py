@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import constants as C
-from .engine import MAX_LOGIT_BIAS, T3Engine, kv_cache_dtype_code, make_guard_params, make_logit_processors, make_sampling
+from .engine import LOGPROBS_MODES, MAX_LOGIT_BIAS, T3Engine, kv_cache_dtype_code, make_guard_params, make_logit_processors, make_sampling
 from .prompt import TextTokenizer, assemble_prompt_ids, find_tokenizer_file
 from .weights import iter_safetensors, synthetic_tensors
 
@@ -31,7 +31,7 @@ MAX_LOGPROBS = 20      # vLLM's default max_logprobs; T3_MAX_LOGPROBS of include
 
 @dataclass
 class Logprob:
-    """vLLM's Logprob: the raw log-probability of an id, its rank among the 8194 speech ids (1 = most likely; ties count for the drawn id)."""
+    """vLLM's Logprob: the log-probability of an id (raw or processed: LLM(logprobs_mode=...)), its rank among the 8194 speech ids (1 = most likely; ties count for the drawn id)."""
     logprob: float
     rank: Optional[int] = None
     decoded_token: Optional[str] = None
@@ -121,9 +121,10 @@ class SamplingParams:
         if bias or allowed is not None or self.min_tokens > 0 or len(stops) > 1:
             self.processors = dict(allowed_ids=allowed, bias=bias, min_tokens=self.min_tokens, extra_stop_ids=stops[1:])
         # vLLM's logprobs: None = off; k in 0..20 = the log-probability and rank of every drawn id plus the k most likely ids per token
-        # (CompletionOutput.logprobs / cumulative_logprob), from a kernel behind the sampler (csrc/t3_logprobs.hip).  Only vLLM's default mode is
-        # built: RAW log-probabilities of the post-CFG logits -- penalties, temperature, top-k / top-p / min-p and the alignment guard's suppression
-        # do not enter.  prompt_logprobs stays ignored and there is no logprobs_mode.
+        # (CompletionOutput.logprobs / cumulative_logprob), from a kernel behind the sampler (csrc/t3_logprobs.hip).  Which numbers is the engine's
+        # LLM(logprobs_mode=...): "raw_logprobs" (vLLM's default: the post-CFG logits -- processors, penalties, temperature and the alignment guard's
+        # suppression do not enter) or "processed_logprobs" (what the draw is taken from; top-k / top-p / min-p enter neither).  prompt_logprobs
+        # stays ignored.
         if logprobs is not None and not 0 <= int(logprobs) <= MAX_LOGPROBS:
             raise ValueError(f"logprobs must be in [0, {MAX_LOGPROBS}], got {logprobs}")
         self.logprobs = None if logprobs is None else int(logprobs)
@@ -157,7 +158,7 @@ class CompletionOutput:
     index: int
     text: str
     token_ids: List[int]
-    cumulative_logprob: Optional[float] = None    # SamplingParams(logprobs=k): the float64 sum of the drawn ids' raw log-probabilities, in token order
+    cumulative_logprob: Optional[float] = None    # SamplingParams(logprobs=k): the float64 sum of the drawn ids' log-probabilities (in the engine's logprobs_mode), in token order
     logprobs: Optional[List[Dict[int, Logprob]]] = None      # ... and per token {offset-space id: Logprob} for the drawn id and the k most likely ids
     finish_reason: Optional[str] = None
     stop_reason: Union[int, str, None] = None
@@ -187,9 +188,13 @@ class LLM:
                  device_id: Optional[int] = None, tokenizer_file: Optional[str] = None, num_hidden_layers: Optional[int] = None,
                  kv_cache_bytes: int = 0, debug_logits: bool = False, honor_enforce_eager: Optional[bool] = None,
                  kv_cache_dtype: Optional[str] = None, alignment_max_text: int = 0,
-                 alignment_guard: Union[bool, dict, None] = None, **kwargs):
+                 alignment_guard: Union[bool, dict, None] = None, logprobs_mode: str = "raw_logprobs", **kwargs):
         if task != "generate":
             raise ValueError("only task='generate' exists on the T3 path")
+        # vLLM's logprobs_mode: what SamplingParams(logprobs=k) reports.  "raw_logprobs" (default) or "processed_logprobs" (the distribution the
+        # sampler draws from, include/t3_engine.h); vLLM's "raw_logits" / "processed_logits" are not built and, like any other string, a ValueError.
+        if logprobs_mode not in LOGPROBS_MODES:
+            raise ValueError(f"logprobs_mode {logprobs_mode!r}: the T3 engine builds {sorted(LOGPROBS_MODES)}")
         if dtype not in ("bfloat16", "auto", torch.bfloat16):
             raise ValueError("the T3 engine computes in bf16 storage / fp32 accumulation only")
         # vLLM's switch for the storage format of the KV cache ("auto" / "bfloat16": bf16; "fp8" / "fp8_e4m3": E4M3 with scale 1.0, half
@@ -237,6 +242,8 @@ class LLM:
         # with that call's parameters
         if alignment_guard not in (None, False):
             self.engine.set_alignment_guard(alignment_guard)
+        if logprobs_mode != "raw_logprobs":
+            self.engine.set_logprobs_mode(logprobs_mode)
         tf = find_tokenizer_file(self.tokenizer_kind, model if model and os.path.isdir(model) else None, tokenizer_file)
         self.tokenizer = TextTokenizer(self.tokenizer_kind, tf) if tf else None
         self._next_id = 0

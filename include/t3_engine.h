@@ -273,6 +273,31 @@ int t3_request_logprobs(T3Handle h, int64_t req_id, int32_t k);
  * top_ids in OFFSET space (speech id + 2500) like t3_get_output.  All four arrays may be NULL to ask for the extents only (each may be NULL on its
  * own).  Error codes as t3_get_alignment. */
 int t3_get_logprobs(T3Handle h, int64_t req_id, float* lp_tok, int32_t* rank, int32_t* top_ids, float* top_lp, int32_t* n_tokens, int32_t* k);
+/* ---- processed log-probabilities: the distribution the sampler draws from -----------------------------------------------------
+ * Mode 1 of t3_set_logprobs_mode.  The raw numbers above stand in front of everything the sampler kernel does to a logit; with the reference defaults
+ * (repetition_penalty 2.0, temperature 0.8) they differ from what is drawn from by whole nats on repeated ids.  In processed mode the records of a
+ * marked request hold, at step k (the step that draws token k) and over the 8194 speech ids v:
+ *   1. x_v = the post-CFG fp32 logit as the sampler forms it (cfg_logit);
+ *   2. steps 1-3 of "logit processors" below, if the request carries processors: allow list, ONE fp32 add per biased id, the stop ids at -inf while
+ *      k < min_tokens;
+ *   3. the guard's SUPPRESS of T3Sampling.stop_token, if the step's control word says so;
+ *   4. the penalties, where cnt_v > 0, in the sampler's fp32 operations and order: x > 0 ? x / repetition_penalty : x * repetition_penalty (skipped at
+ *      1.0), then x - frequency_penalty * cnt_v, then x - presence_penalty.  cnt_v is the count the step's sampler used for its own draw: the
+ *      kernel runs behind it and takes the drawn id's increment back (a stored 65535 counts as saturated before the draw; the engine's counts stay
+ *      below 8192, its largest max_model_len);
+ *   5. z_v = x_v / T, T = temperature, or 1 where temperature < 1e-5 (greedy), as vLLM substitutes;
+ *   6. lp_v = (z_v - M) - logf(Z),  M = max_v z_v,  Z = sum_v exp(z_v - M) in fp32, in the fixed order of the raw kernel;
+ *   7. rank = #{v : z_v >= z_tok};
+ *   8. top[i] = the ids ordered by (z_v descending, v ascending), decided on the exact fp32 z.
+ * Ids at -inf have lp = -inf and enter the top list only when no finite id is left.  A guard-FORCEd stop id reports its z like any other id: -inf if
+ * the processors had masked it.  min-p, top-k and top-p are NOT applied.  This is the project's own definition: vLLM is not part of the reference
+ * tree and its versions disagree on where "processed" is captured.  With top_p = 1, top_k = 0, min_p = 0 it is exactly the distribution of the draw.
+ * Token ids never depend on the mode; in mode 0 every record is what it was before the mode existed, and a step that samples no marked request
+ * launches exactly what it launches without the feature.  The records keep the raw kernel's guarantees: bit-identical between eager steps, captured
+ * graphs, bursts and batch compositions.
+ * t3_set_logprobs_mode: mode 0 = raw (the default), 1 = processed; any other value is T3_E_INVALID.  Valid only while nothing is queued or running
+ * (T3_E_STATE).  Drops the captured step graphs.  The mode holds for every request marked from then on. */
+int t3_set_logprobs_mode(T3Handle h, int32_t mode);
 
 /* ---- logit processors -------------------------------------------------------------------------------------------------------
  * vLLM's SamplingParams(allowed_token_ids=, logit_bias=, bad_words= (single ids), min_tokens=, stop_token_ids=) inside the sampler kernel: the
@@ -431,6 +456,11 @@ int t3k_align_scores(const float* a, int32_t* w, int32_t n);
  * 8), token = the drawn speech-space id, k in 0..T3_MAX_LOGPROBS.  top_ids (SPEECH-space) / top_lp [k], nullable when k = 0. */
 int t3k_logprobs(const void* logits2_bf16, int32_t ldl, float cfg, int32_t token, int32_t k, int32_t* rank, float* lp_tok,
                  int32_t* top_ids, float* top_lp);
+/* Its processed instantiation for one utterance at step `step` (< 8192).  counts uint16 [8194] = the counts the step's sampler USED for its draw (the
+ * hook raises the drawn id's count on its device copy, as the sampler leaves it in the engine); lp nullable = no processors, else checked as
+ * t3_request_logit_processors checks it; ctl = -1 no control word, 0 / 1 / 2 = the guard's word for a slot marked guarded (as t3k_sample_ctl). */
+int t3k_logprobs_processed(const void* logits2_bf16, int32_t ldl, float cfg, const uint16_t* counts, const T3Sampling* sp, const T3LogitProcessors* lp,
+                           int32_t ctl, uint32_t step, int32_t token, int32_t k, int32_t* rank, float* lp_tok, int32_t* top_ids, float* top_lp);
 /* ---- the FP8 (E4M3FN) KV pool, kv_cache_dtype = 1 ----
  * y = dequantised q8(x) on the device, q8(x) = e4m3fn(round-to-nearest-even(clamp(x, -448, 448))): the stored format of the FP8 pool. */
 int t3k_fp8_roundtrip(const float* x, float* y, int32_t n);
