@@ -38,6 +38,7 @@ namespace {
 struct LayerW {
     uint16_t *qkv = nullptr, *o = nullptr, *gu = nullptr, *down = nullptr;  // device, packed (qkv / gu carry their RMSNorm weight, fold_norm_weight)
     std::vector<uint16_t> h_q, h_k, h_v, h_g, h_u, h_ln1, h_ln2;   // host staging until finalize
+    std::vector<uint16_t> h_o, h_d;   // o / down as loaded, kept until finalize: t3_set_weight_dtype may still turn them into MXFP8
     bool have_o = false, have_d = false;
 };
 
@@ -103,6 +104,7 @@ struct T3Engine {
     // KV pool + tables
     unsigned char* kv = nullptr;   // the paged pool, sized in bytes per block: bf16 2 bytes per element, FP8 E4M3 1, MXFP4 half a byte and its scales
     int kv_dtype = 0;              // cfg.kv_cache_dtype: 0 bf16, 1 FP8, 4 MXFP4
+    int w_dtype = 0;               // t3_set_weight_dtype: 0 bf16, 1 MXFP8 (the four layer matrices; t3_gemm_mx8.hip)
     size_t kv_block_bytes = (size_t)KV_BLOCK_ELEMS * 2;   // per layer per block, padding included
     int kv_token_bytes = 2 * H * HD * 2;                  // per layer per token, what a decode step streams: 4096 / 2048 / 1088
     std::vector<int> free_blocks;
@@ -214,7 +216,8 @@ struct T3Engine {
     int fail(int code, const std::string& m) { err = m; return code; }
     // algorithmic weight bytes streamed once per step (SURVEY.md 8(d) "W"): bf16 backbone incl. norms + speech head
     double weight_bytes_for_step() const {
-        const double per_layer = (4.0 * D * D + 3.0 * F * D + 2.0 * D) * 2.0;
+        const double mat = 4.0 * D * D + 3.0 * F * D;              // MXFP8: a byte per weight and a scale byte per 32
+        const double per_layer = (w_dtype == 1 ? mat * (33.0 / 32.0) : mat * 2.0) + 2.0 * D * 2.0;
         return cfg.n_layers * per_layer + D * 2.0 + (double)V * D * 2.0;
     }
 };
@@ -331,6 +334,13 @@ static int upload(T3Engine* e, const uint16_t* host, size_t elems, uint16_t** de
     e->weight_bytes += (int64_t)elems * 2;
     return T3_OK;
 }
+static int upload_bytes(T3Engine* e, const unsigned char* host, size_t bytes, uint16_t** dev) {
+    free_dev(*dev); *dev = nullptr;
+    if (hipMalloc((void**)dev, bytes) != hipSuccess) return e->fail(T3_E_NOMEM, "hipMalloc (weight) failed");
+    if (hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice) != hipSuccess) return e->fail(T3_E_DEVICE, "hipMemcpy H2D (weight) failed");
+    e->weight_bytes += (int64_t)bytes;
+    return T3_OK;
+}
 static int upload_packed(T3Engine* e, const uint16_t* W, int N, int K, int Npad, uint16_t** dev) {
     std::vector<uint16_t> p((size_t)Npad * K);
     pack_weight(W, N, K, Npad, p.data());
@@ -349,7 +359,6 @@ extern "C" int t3_load_tensor(T3Handle e, const char* name, const void* data, in
         if (L < 0 || L >= e->cfg.n_layers) return e->fail(T3_E_NOTFOUND, std::string("layer index beyond n_layers: ") + name);
         LayerW& y = e->layers[L];
         std::string r(rest);
-        int rc;
         if (r == "self_attn.q_proj.weight" || r == "self_attn.k_proj.weight" || r == "self_attn.v_proj.weight") {
             if (!need(D, D)) return e->fail(T3_E_INVALID, std::string("bad shape for ") + name);
             auto& dst = r[10] == 'q' ? y.h_q : r[10] == 'k' ? y.h_k : y.h_v;
@@ -361,13 +370,11 @@ extern "C" int t3_load_tensor(T3Handle e, const char* name, const void* data, in
         }
         if (r == "self_attn.o_proj.weight") {
             if (!need(D, D)) return e->fail(T3_E_INVALID, std::string("bad shape for ") + name);
-            if ((rc = to_host(e, data, bytes, host))) return rc;
-            y.have_o = true; return upload_packed(e, host.data(), D, D, D, &y.o);
+            y.have_o = true; return to_host(e, data, bytes, y.h_o);
         }
         if (r == "mlp.down_proj.weight") {
             if (!need(D, F)) return e->fail(T3_E_INVALID, std::string("bad shape for ") + name);
-            if ((rc = to_host(e, data, bytes, host))) return rc;
-            y.have_d = true; return upload_packed(e, host.data(), D, F, D, &y.down);
+            y.have_d = true; return to_host(e, data, bytes, y.h_d);
         }
         if (r == "input_layernorm.weight" || r == "post_attention_layernorm.weight") {
             if ((size_t)rows * cols != (size_t)D) return e->fail(T3_E_INVALID, std::string("bad shape for ") + name);
@@ -407,6 +414,14 @@ static int dalloc(T3Engine* e, T** p, size_t n, bool zero = false) {
     return T3_OK;
 }
 
+extern "C" int t3_set_weight_dtype(T3Handle e, int32_t dtype) {
+    if (!e) return T3_E_INVALID;
+    if (dtype != 0 && dtype != 1) return e->fail(T3_E_INVALID, "weight dtype must be 0 (bf16) or 1 (mxfp8)");
+    if (e->finalized) return e->fail(T3_E_STATE, "t3_set_weight_dtype after t3_finalize_weights");
+    e->w_dtype = dtype;
+    return T3_OK;
+}
+
 extern "C" int t3_finalize_weights(T3Handle e) {
     if (!e) return T3_E_INVALID;
     if (e->finalized) return T3_OK;
@@ -423,14 +438,29 @@ extern "C" int t3_finalize_weights(T3Handle e) {
         memcpy(w.data() + (size_t)D * D, y.h_k.data(), (size_t)D * D * 2);
         memcpy(w.data() + (size_t)2 * D * D, y.h_v.data(), (size_t)D * D * 2);
         fold_norm_weight(w.data(), QKV, D, y.h_ln1.data(), w.data());
-        pack_weight(w.data(), QKV, D, QKV, p.data());
-        if ((rc = upload(e, p.data(), p.size(), &y.qkv))) return rc;
         fold_norm_weight(y.h_g.data(), F, D, y.h_ln2.data(), y.h_g.data());
         fold_norm_weight(y.h_u.data(), F, D, y.h_ln2.data(), y.h_u.data());
-        std::vector<uint16_t> g((size_t)2 * F * D);
-        pack_gate_up(y.h_g.data(), y.h_u.data(), F, D, g.data());
-        if ((rc = upload(e, g.data(), g.size(), &y.gu))) return rc;
-        for (auto* v : {&y.h_q, &y.h_k, &y.h_v, &y.h_g, &y.h_u, &y.h_ln1, &y.h_ln2}) { v->clear(); v->shrink_to_fit(); }
+        if (e->w_dtype == 1) {
+            // MXFP8: the four matrices are quantised here, behind the fold, and packed for gemm_mx8_kernel (t3_gemm_mx8.hip)
+            std::vector<unsigned char> b(mx8_packed_bytes(2 * F, D));
+            pack_weight_mx8(w.data(), QKV, D, 8, b.data());
+            if ((rc = upload_bytes(e, b.data(), mx8_packed_bytes(QKV, D), &y.qkv))) return rc;
+            pack_weight_mx8(y.h_o.data(), D, D, 2, b.data());
+            if ((rc = upload_bytes(e, b.data(), mx8_packed_bytes(D, D), &y.o))) return rc;
+            pack_gate_up_mx8(y.h_g.data(), y.h_u.data(), F, D, b.data());
+            if ((rc = upload_bytes(e, b.data(), mx8_packed_bytes(2 * F, D), &y.gu))) return rc;
+            pack_weight_mx8(y.h_d.data(), D, F, 8, b.data());
+            if ((rc = upload_bytes(e, b.data(), mx8_packed_bytes(D, F), &y.down))) return rc;
+        } else {
+            pack_weight(w.data(), QKV, D, QKV, p.data());
+            if ((rc = upload(e, p.data(), p.size(), &y.qkv))) return rc;
+            if ((rc = upload_packed(e, y.h_o.data(), D, D, D, &y.o))) return rc;
+            std::vector<uint16_t> g((size_t)2 * F * D);
+            pack_gate_up(y.h_g.data(), y.h_u.data(), F, D, g.data());
+            if ((rc = upload(e, g.data(), g.size(), &y.gu))) return rc;
+            if ((rc = upload_packed(e, y.h_d.data(), D, F, D, &y.down))) return rc;
+        }
+        for (auto* v : {&y.h_q, &y.h_k, &y.h_v, &y.h_g, &y.h_u, &y.h_ln1, &y.h_ln2, &y.h_o, &y.h_d}) { v->clear(); v->shrink_to_fit(); }
     }
     {
         fold_norm_weight(e->h_head.data(), V, D, e->h_norm.data(), e->h_head.data());
@@ -669,11 +699,18 @@ static int launch_embed_phase(T3Engine* e, T3Engine::Group& g, const T3Engine::S
     if (e->d_dbg_emb) HIP_TRY(hipMemcpyAsync(e->d_dbg_emb, g.h, (size_t)sr.M * D * 2, hipMemcpyDeviceToDevice, s));
     return T3_OK;
 }
+// the arguments of a projection over MXFP8 weights: `rows` packed rows of K octets, their scale bytes behind them
+static Mx8GemmArgs mx8_args(const uint16_t* x, const uint16_t* w, int M, int K, int N, int rows, void* out, int ldo) {
+    const unsigned char* b = reinterpret_cast<const unsigned char*>(w);
+    return Mx8GemmArgs{x, reinterpret_cast<const uint4*>(b), b + (size_t)rows * K, M, K, N, out, ldo};
+}
 static int launch_qkv_phase(T3Engine* e, T3Engine::Group& g, const T3Engine::StepRec& sr, int L, hipStream_t s) {
     LayerW& y = e->layers[L];
     const int M = sr.M;
     // 5 launches per layer: RMSNorm is folded into the qkv / gate-up GEMMs, the residual add into the o / down GEMMs
-    Prof p(e, K_QKV, s); GemmArgs a{g.h, (const uint4*)y.qkv, M, D, QKV, g.qkv, QKV, 4, 1, nullptr, 0, g.rstd};
+    Prof p(e, K_QKV, s);
+    if (e->w_dtype == 1) { HIP_TRY(launch_gemm_mx8(mx8_args(g.h, y.qkv, M, D, QKV, QKV, g.qkv, QKV), EPI_BF16, s)); return T3_OK; }
+    GemmArgs a{g.h, (const uint4*)y.qkv, M, D, QKV, g.qkv, QKV, 4, 1, nullptr, 0, g.rstd};
     HIP_TRY(launch_gemm(a, EPI_BF16, choose_mt(M, QKV / 16, 4, true), s));
     return T3_OK;
 }
@@ -721,6 +758,12 @@ static int launch_alignment_phase(T3Engine* e, T3Engine::Group& g, const T3Engin
 static int launch_mlp_phase(T3Engine* e, T3Engine::Group& g, const T3Engine::StepRec& sr, int L, hipStream_t s) {
     LayerW& y = e->layers[L];
     const int M = sr.M;
+    if (e->w_dtype == 1) {
+        { Prof p(e, K_O, s); HIP_TRY(launch_gemm_mx8(mx8_args(g.att, y.o, M, D, D, D, g.h, D), EPI_RESID, s)); }
+        { Prof p(e, K_GU, s); HIP_TRY(launch_gemm_mx8(mx8_args(g.h, y.gu, M, D, F, 2 * F, g.act, F), EPI_SILU, s)); }
+        { Prof p(e, K_DOWN, s); HIP_TRY(launch_gemm_mx8(mx8_args(g.act, y.down, M, F, D, D, g.h, D), EPI_RESID, s)); }
+        return T3_OK;
+    }
     { Prof p(e, K_O, s); GemmArgs a{g.att, (const uint4*)y.o, M, D, D, g.h, D, 16, 0, nullptr}; HIP_TRY(launch_gemm(a, EPI_RESID, choose_mt(M, D / 16, 16, false), s)); }
     {
         Prof p(e, K_GU, s); GemmArgs a{g.h, (const uint4*)y.gu, M, D, F, g.act, F, 4, 1, nullptr, 0, g.rstd};

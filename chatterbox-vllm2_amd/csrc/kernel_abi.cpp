@@ -154,6 +154,49 @@ extern "C" int t3k_silu_mul_gemm(const void* h, const void* ln_w, const void* wg
     return T3_OK;
 }
 
+// ---- the layer projections over MXFP8 weights (t3_gemm_mx8.hip): the arguments of their bf16 twins above; each folds the norm weight where its
+// twin does, quantises and packs as t3_finalize_weights does under t3_set_weight_dtype = 1, and runs the kernel the engine runs
+extern "C" int t3k_mxfp8_roundtrip(const void* w, void* y, int32_t rows, int32_t cols) {
+    if (!w || !y || rows <= 0 || cols <= 0 || cols % 32) return T3_E_INVALID;
+    mx8_roundtrip((const uint16_t*)w, (uint16_t*)y, rows, cols);
+    return T3_OK;
+}
+static int mx8_run(const void* x, const std::vector<unsigned char>& packed, int rows, int M, int K, int N, int epi, void* out, bool out_is_input) {
+    if (!have_device()) return T3_E_DEVICE;
+    if (prepare_gemm_mx8() != hipSuccess) return T3_E_DEVICE;
+    DevBuf dx, dw, dout;
+    K_TRY(dx.from(x, (size_t)M * K * 2)); K_TRY(dw.from(packed.data(), packed.size()));
+    if (out_is_input) K_TRY(dout.from(out, (size_t)M * N * 2)); else K_TRY(dout.alloc((size_t)M * N * 2, true));
+    Mx8GemmArgs a{dx.as<uint16_t>(), dw.as<uint4>(), dw.as<unsigned char>() + (size_t)rows * K, M, K, N, dout.p, N};
+    K_TRY(launch_gemm_mx8(a, epi, nullptr));
+    K_TRY(hipDeviceSynchronize());
+    K_TRY(hipMemcpy(out, dout.p, (size_t)M * N * 2, hipMemcpyDeviceToHost));
+    return T3_OK;
+}
+extern "C" int t3k_qkv_gemm_mx8(const void* h, const void* ln_w, const void* w, int32_t M, void* out_bf16) {
+    if (!h || !ln_w || !w || !out_bf16 || M <= 0) return T3_E_INVALID;
+    std::vector<uint16_t> folded((size_t)QKV * D);
+    std::vector<unsigned char> packed(mx8_packed_bytes(QKV, D));
+    fold_norm_weight((const uint16_t*)w, QKV, D, (const uint16_t*)ln_w, folded.data());
+    pack_weight_mx8(folded.data(), QKV, D, 8, packed.data());
+    return mx8_run(h, packed, QKV, M, D, QKV, EPI_BF16, out_bf16, false);
+}
+extern "C" int t3k_gemm_resid_mx8(const void* x, const void* w, int32_t M, int32_t K, int32_t N, void* h_bf16) {
+    if (!x || !w || !h_bf16 || M <= 0 || N <= 0 || N % 16 || (K != D && K != F)) return T3_E_INVALID;
+    std::vector<unsigned char> packed(mx8_packed_bytes(N, K));
+    pack_weight_mx8((const uint16_t*)w, N, K, K == D ? 2 : 8, packed.data());
+    return mx8_run(x, packed, N, M, K, N, EPI_RESID, h_bf16, true);
+}
+extern "C" int t3k_silu_mul_gemm_mx8(const void* h, const void* ln_w, const void* wg, const void* wu, int32_t M, int32_t Fd, void* out) {
+    if (!h || !ln_w || !wg || !wu || !out || M <= 0 || Fd <= 0 || Fd % 16) return T3_E_INVALID;
+    std::vector<uint16_t> fg((size_t)Fd * D), fu((size_t)Fd * D);
+    std::vector<unsigned char> packed(mx8_packed_bytes(2 * Fd, D));
+    fold_norm_weight((const uint16_t*)wg, Fd, D, (const uint16_t*)ln_w, fg.data());
+    fold_norm_weight((const uint16_t*)wu, Fd, D, (const uint16_t*)ln_w, fu.data());
+    pack_gate_up_mx8(fg.data(), fu.data(), Fd, D, packed.data());
+    return mx8_run(h, packed, 2 * Fd, M, D, Fd, EPI_SILU, out, false);
+}
+
 // fmt 1 / 4: the same call over an FP8 (E4M3) / MXFP4 pool -- byte pools, their own launchers; kv_out (nullable) [rows][2][1024] = the stored K / V read back
 static int rope_attention_impl(const void* qkv, const int32_t* row_stream, const int32_t* row_pos, int32_t rows,
                                int32_t n_streams, int32_t max_pos, void* out, int fmt, void* kv_out) {

@@ -76,6 +76,26 @@ hipError_t launch_gemm(const GemmArgs& a, int epi, int mt, hipStream_t s);
 void set_pgemm_min_rows(int rows);   // row count from which launch_gemm takes the prefill schedule (process-wide; < 0 = default)
 void set_pgemm_wide_rows(int rows);  // row count from which its 4-segment forms take 128 x 128 tiles (0 = never; < 0 = default 2048)
 
+// The layer projections over MXFP8 weights (t3_gemm_mx8.hip, t3_set_weight_dtype = 1): format, packed layout and schedule stand at the head of that
+// file.  epi: EPI_BF16 (qkv) / EPI_SILU (gate/up; N = F) with the RMSNorm statistic and rstd, K = 1024, 4 segments; EPI_RESID with 16 segments,
+// K = 1024 (o) or 4096 (down).  N a multiple of 16, ldo even.
+struct Mx8GemmArgs {
+    const uint16_t* X;         // [M][K] bf16 row-major
+    const uint4* Wq;           // packed E4M3 octets (pack_weight_mx8)
+    const unsigned char* Ws;   // their E8M0 scale bytes: Wq's bytes + rows * K, rows = N (EPI_SILU: 2 F)
+    int M, K, N;
+    void* out;                 // bf16 [M][ldo]; EPI_RESID: the residual stream, updated in place
+    int ldo;
+};
+hipError_t launch_gemm_mx8(const Mx8GemmArgs& a, int epi, hipStream_t s);
+hipError_t prepare_gemm_mx8();      // dynamic-LDS limits of its instantiations (before any stream capture)
+// host: y = the stored value of w, blocks of 32 along a row (cols a multiple of 32) -- the quantiser pack_weight_mx8 runs, and its inverse
+void mx8_roundtrip(const uint16_t* w, uint16_t* y, int rows, int cols);
+size_t mx8_packed_bytes(int N, int K);                    // octets + scale bytes of an [N][K] matrix: 8.25 bits per weight
+// host: [N][K] bf16 (N a multiple of 16, K of 64) -> out[mx8_packed_bytes(N, K)]; kbs = k-blocks of 32 per K segment of the form that reads it (8; o: 2)
+void pack_weight_mx8(const uint16_t* W, int N, int K, int kbs, unsigned char* out);
+void pack_gate_up_mx8(const uint16_t* Wg, const uint16_t* Wu, int Fdim, int K, unsigned char* out);      // tiles interleaved as pack_gate_up's
+
 // Per-row record of a step (int32 words), built by the scheduler and uploaded once per step:
 //   [0] stream  [1] position  [2] embed kind  [3] embed a  [4] embed b  [5] alignment frame  [6] alignment n_text  [7] unused  [8 ..] KV block ids of the row's stream
 // One lookup gives a kernel everything it needs to address the row's paged KV (no stream -> block-table hop).

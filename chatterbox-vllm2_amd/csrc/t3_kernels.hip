@@ -657,6 +657,7 @@ hipError_t prepare_kernels() {
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(sampler_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(sampler_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds + PROC_LDS));
     if (e == hipSuccess) e = prepare_gemm2();
+    if (e == hipSuccess) e = prepare_gemm_mx8();
     if (e == hipSuccess) done[cur_device()] = true;
     return e;
 }

@@ -133,6 +133,7 @@ ABI_SYMBOLS = [
     "t3k_gemm", "t3k_norm_gemm", "t3k_qkv_gemm", "t3k_head_gemm", "t3k_gemm_resid", "t3k_silu_mul_gemm", "t3k_rope_attention", "t3k_decode_attention", "t3k_sample", "t3k_sample_support", "t3k_expf",
     "t3k_fp8_roundtrip", "t3k_rope_attention_fp8", "t3k_decode_attention_fp8",
     "t3k_fp4_roundtrip", "t3k_rope_attention_fp4", "t3k_decode_attention_fp4",
+    "t3_set_weight_dtype", "t3k_mxfp8_roundtrip", "t3k_qkv_gemm_mx8", "t3k_gemm_resid_mx8", "t3k_silu_mul_gemm_mx8",
     "t3_reserve_alignment", "t3_set_alignment_heads", "t3_get_alignment", "t3k_attention_probs",
     "t3_set_alignment_guard", "t3_get_guard", "t3k_alignment_guard", "t3k_sample_ctl",
     "t3_reserve_logprobs", "t3_request_logprobs", "t3_get_logprobs", "t3k_logprobs", "t3_set_logprobs_mode", "t3k_logprobs_processed",
@@ -210,6 +211,11 @@ def load_library():
     L.t3k_fp4_roundtrip.argtypes = [vp, vp, i32]
     L.t3k_rope_attention_fp4.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     L.t3k_decode_attention_fp4.argtypes = [vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp]
+    L.t3_set_weight_dtype.argtypes = [vp, i32]
+    L.t3k_mxfp8_roundtrip.argtypes = [vp, vp, i32, i32]
+    L.t3k_qkv_gemm_mx8.argtypes = [vp, vp, vp, i32, vp]
+    L.t3k_gemm_resid_mx8.argtypes = [vp, vp, i32, i32, i32, vp]
+    L.t3k_silu_mul_gemm_mx8.argtypes = [vp, vp, vp, vp, i32, i32, vp]
     L.t3_reserve_alignment.argtypes = [vp, i32]
     L.t3_set_alignment_heads.argtypes = [vp, vp, i32]
     L.t3_get_alignment.argtypes = [vp, i64, vp, ct.POINTER(i32), ct.POINTER(i32)]
@@ -285,14 +291,31 @@ def kv_cache_dtype_code(name) -> int:
     return KV_CACHE_DTYPES[name]
 
 
+# storage formats of the four layer projections' weights (t3_set_weight_dtype)
+WEIGHT_DTYPES = {"bf16": 0, "mxfp8": 1}
+
+
+def weight_dtype_code(name) -> int:
+    """'bf16' / 'mxfp8' -> t3_set_weight_dtype; None = the T3_WEIGHT_DTYPE environment variable, else bf16."""
+    if name is None:
+        name = os.environ.get("T3_WEIGHT_DTYPE", "bf16")
+    if name not in WEIGHT_DTYPES:
+        raise ValueError(f"weight_dtype {name!r}: the T3 engine stores the layer projections as {sorted(WEIGHT_DTYPES)}")
+    return WEIGHT_DTYPES[name]
+
+
 class T3Engine:
     """Thin object wrapper over one engine handle (one GPU)."""
 
     def __init__(self, n_layers: int = C.N_LAYERS, text_vocab: int = C.TEXT_VOCAB_EN, max_model_len: int = 1000,
                  max_seqs: int = 32, device_id: int = 0, kv_bytes: int = 0, gpu_memory_utilization: float = 0.9,
                  cfg_scale: Optional[float] = None, enforce_eager: bool = True, debug_logits: bool = False,
-                 max_batched_rows: int = 0, n_groups: int = 0, kv_cache_dtype: Optional[str] = None):
+                 max_batched_rows: int = 0, n_groups: int = 0, kv_cache_dtype: Optional[str] = None,
+                 weight_dtype: Optional[str] = None):
+        """weight_dtype: "bf16", or "mxfp8" = the qkv / o / gate-up / down matrices quantised to OCP MXFP8 at finalize() (8.25 bits per weight; the
+        speech head and the embeddings stay bf16).  Audio quality under MXFP8 has not been validated on a real checkpoint."""
         kv_code = kv_cache_dtype_code(kv_cache_dtype)
+        w_code = weight_dtype_code(weight_dtype)
         self.lib = load_library()
         if cfg_scale is None:
             cfg_scale = float(os.environ.get("CHATTERBOX_CFG_SCALE", "0.5"))   # t3.py:296
@@ -308,6 +331,8 @@ class T3Engine:
         rc = self.lib.t3_create(ct.byref(self.cfg), ct.byref(self.h))
         if rc:
             _raise(rc, self.lib.t3_last_error(None).decode())
+        if w_code:
+            self._chk(self.lib.t3_set_weight_dtype(self.h, w_code))
 
     def _chk(self, rc: int):
         if rc:
@@ -600,6 +625,39 @@ def k_qkv_gemm(h: torch.Tensor, ln_w: torch.Tensor, W: torch.Tensor) -> torch.Te
     assert tuple(W.shape) == (3072, C.HIDDEN)
     out = torch.empty(h.shape[0], 3072, dtype=torch.bfloat16)
     _chk_k(load_library().t3k_qkv_gemm(h.data_ptr(), ln_w.data_ptr(), W.data_ptr(), h.shape[0], out.data_ptr()), "t3k_qkv_gemm")
+    return out
+
+
+def k_mxfp8_roundtrip(W: torch.Tensor) -> torch.Tensor:
+    """The stored value of every weight under the MXFP8 format of finalize() (host code; blocks of 32 along a row) -> bf16, W's shape"""
+    W = _bf(W)
+    y = torch.empty_like(W)
+    _chk_k(load_library().t3k_mxfp8_roundtrip(W.data_ptr(), y.data_ptr(), W.shape[0], W.shape[1]), "t3k_mxfp8_roundtrip")
+    return y
+
+
+def k_qkv_gemm_mx8(h: torch.Tensor, ln_w: torch.Tensor, W: torch.Tensor) -> torch.Tensor:
+    """k_qkv_gemm over MXFP8 weights (quantised as finalize() does, the engine's kernel) -> [M, 3072] bf16"""
+    h, ln_w, W = _bf(h), _bf(ln_w), _bf(W)
+    assert tuple(W.shape) == (3072, C.HIDDEN)
+    out = torch.empty(h.shape[0], 3072, dtype=torch.bfloat16)
+    _chk_k(load_library().t3k_qkv_gemm_mx8(h.data_ptr(), ln_w.data_ptr(), W.data_ptr(), h.shape[0], out.data_ptr()), "t3k_qkv_gemm_mx8")
+    return out
+
+
+def k_gemm_resid_mx8(x: torch.Tensor, W: torch.Tensor, h: torch.Tensor) -> torch.Tensor:
+    """k_gemm_resid over MXFP8 weights."""
+    x, W = _bf(x), _bf(W); h = _bf(h).clone()
+    _chk_k(load_library().t3k_gemm_resid_mx8(x.data_ptr(), W.data_ptr(), x.shape[0], x.shape[1], W.shape[0], h.data_ptr()), "t3k_gemm_resid_mx8")
+    return h
+
+
+def k_silu_mul_gemm_mx8(h: torch.Tensor, ln_w: torch.Tensor, Wg: torch.Tensor, Wu: torch.Tensor) -> torch.Tensor:
+    """k_silu_mul_gemm over MXFP8 weights."""
+    h, ln_w, Wg, Wu = _bf(h), _bf(ln_w), _bf(Wg), _bf(Wu)
+    M, Fd = h.shape[0], Wg.shape[0]
+    out = torch.empty(M, Fd, dtype=torch.bfloat16)
+    _chk_k(load_library().t3k_silu_mul_gemm_mx8(h.data_ptr(), ln_w.data_ptr(), Wg.data_ptr(), Wu.data_ptr(), M, Fd, out.data_ptr()), "t3k_silu_mul_gemm_mx8")
     return out
 
 

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import constants as C
-from .engine import LOGPROBS_MODES, MAX_LOGIT_BIAS, T3Engine, kv_cache_dtype_code, make_guard_params, make_logit_processors, make_sampling
+from .engine import LOGPROBS_MODES, MAX_LOGIT_BIAS, T3Engine, kv_cache_dtype_code, weight_dtype_code, make_guard_params, make_logit_processors, make_sampling
 from .prompt import TextTokenizer, assemble_prompt_ids, find_tokenizer_file
 from .weights import iter_safetensors, synthetic_tensors
 
@@ -188,7 +188,8 @@ class LLM:
                  device_id: Optional[int] = None, tokenizer_file: Optional[str] = None, num_hidden_layers: Optional[int] = None,
                  kv_cache_bytes: int = 0, debug_logits: bool = False, honor_enforce_eager: Optional[bool] = None,
                  kv_cache_dtype: Optional[str] = None, alignment_max_text: int = 0,
-                 alignment_guard: Union[bool, dict, None] = None, logprobs_mode: str = "raw_logprobs", **kwargs):
+                 alignment_guard: Union[bool, dict, None] = None, logprobs_mode: str = "raw_logprobs",
+                 quantization: Optional[str] = None, **kwargs):
         if task != "generate":
             raise ValueError("only task='generate' exists on the T3 path")
         # vLLM's logprobs_mode: what SamplingParams(logprobs=k) reports.  "raw_logprobs" (default) or "processed_logprobs" (the distribution the
@@ -201,6 +202,13 @@ class LLM:
         # the bytes per token; "mxfp4" / "fp4": E2M1 with one power-of-two scale per 32 head dims of a token, 1088 bytes per token and layer
         # against 4096; anything else, "fp8_e5m2" included, is a ValueError).  None: the T3_KV_CACHE_DTYPE environment variable.
         kv_cache_dtype_code(kv_cache_dtype)
+        # vLLM's switch for quantised weights.  "mxfp8": the qkv / o / gate-up / down matrices of every layer are quantised to OCP MXFP8 while the
+        # checkpoint loads (E4M3 elements, one power-of-two scale per 32 weights of a row: 8.25 bits per weight); the speech head and the embeddings
+        # stay bf16.  Audio quality under it has not been validated on a real checkpoint.  None: the T3_WEIGHT_DTYPE environment variable
+        # ("bf16" / "mxfp8"), else bf16.  Any other method ("awq", "gptq", "fp8", ...) is not built: a ValueError.
+        if quantization is not None and quantization != "mxfp8":
+            raise ValueError(f"quantization {quantization!r}: the T3 engine builds 'mxfp8' only (None = bf16 weights)")
+        weight_dtype_code(quantization)
         for k in kwargs:
             warnings.warn(f"LLM(...) keyword {k!r} has no meaning for the T3 engine and is ignored")
         self.model_dir = model
@@ -225,7 +233,7 @@ class LLM:
         self.engine = T3Engine(n_layers=n_layers, text_vocab=text_vocab, max_model_len=max_model_len, max_seqs=max_num_seqs,
                                device_id=device_id, kv_bytes=kv_cache_bytes, gpu_memory_utilization=gpu_memory_utilization,
                                enforce_eager=eager, debug_logits=debug_logits, max_batched_rows=max_num_batched_tokens,
-                               kv_cache_dtype=kv_cache_dtype)
+                               kv_cache_dtype=kv_cache_dtype, weight_dtype=quantization)
         ckpt = os.path.join(model, "model.safetensors") if model and os.path.isdir(model) else model
         if load_format == "dummy" or not (ckpt and os.path.exists(ckpt)):
             if load_format != "dummy":

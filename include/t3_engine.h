@@ -479,6 +479,23 @@ int t3k_rope_attention_fp4(const void* qkv_bf16, const int32_t* row_stream, cons
                            int32_t n_streams, int32_t max_pos, void* out_bf16, void* kv_bf16);
 int t3k_decode_attention_fp4(const void* ctx_qkv_bf16, int32_t n_content, int32_t content_rows, const void* new_qkv_bf16, const int32_t* ctx,
                              int32_t rows, int32_t steps, int32_t max_pos, int32_t waves, void* out_bf16, void* kv_new_bf16);
+/* ---- MXFP8 weights for the four layer projections (qkv, o, gate/up, down), t3_set_weight_dtype = 1 ----
+ * Storage format of t3_finalize_weights, applied behind the RMSNorm fold: blocks of 32 consecutive k of one output row; with E the biased exponent
+ * field of the block's max |w|, b = max(E - 8, 0) is the block's E8M0 scale byte, X = 2^(b - 127), an element is q8(w / X) (q8 as above) and the
+ * stored value is X * element: 8.25 bits per weight.  Every stored value of a block in bf16's normal range is a bf16 value, and the kernels
+ * (t3_gemm_mx8.hip) rebuild it exactly in front of the bf16 matrix instruction, so a step computes bit for bit what the bf16 engine computes over
+ * the stored values.  The speech head, the embeddings and the position tables stay bf16.  Audio quality under this format has NOT been
+ * validated on a real checkpoint.
+ * dtype: 0 = bf16 (default), 1 = MXFP8, anything else T3_E_INVALID; T3_E_STATE after t3_finalize_weights. */
+int t3_set_weight_dtype(T3Handle h, int32_t dtype);
+/* y = the stored value of w: the finalize quantiser and its inverse, on the host.  w, y bf16 [rows][cols], cols a multiple of 32. */
+int t3k_mxfp8_roundtrip(const void* w_bf16, void* y_bf16, int32_t rows, int32_t cols);
+/* t3k_qkv_gemm / t3k_gemm_resid (K = 1024 or 4096) / t3k_silu_mul_gemm over MXFP8 weights: the same arguments; each takes bf16 weights, folds the norm
+ * weight where its twin does, quantises as t3_finalize_weights does and runs the kernel a step runs. */
+int t3k_qkv_gemm_mx8(const void* h_bf16, const void* ln_w_bf16, const void* w_bf16, int32_t M, void* out_bf16);
+int t3k_gemm_resid_mx8(const void* x_bf16, const void* w_bf16, int32_t M, int32_t K, int32_t N, void* h_bf16);
+int t3k_silu_mul_gemm_mx8(const void* h_bf16 /*[M][1024]*/, const void* ln_w_bf16, const void* wg_bf16 /*[F][1024]*/, const void* wu_bf16,
+                          int32_t M, int32_t F, void* out_bf16 /*[M][F]*/);
 /* The alignment tap kernel (t3_alignment.hip) on host buffers.  Every row is written through the prefill path (RoPE + paged write, as
  * t3k_rope_attention / t3k_rope_attention_fp8 / _fp4 do; kv_dtype 0 = bf16 pool, 1 = FP8, 4 = MXFP4), then the tap runs for EVERY row over the span [lo, hi) of
  * its stream: out [rows][hi - lo] = softmax over the row's context 0 .. row_pos of head `head`; positions at or beyond the row's own context
